@@ -2,7 +2,11 @@
 BASELINE.json configs[1] (C2: Linear(1024,2688)-ReLU-Linear(2688,2688)-ReLU-Linear(2688,10),
 D = 10 010 122, MSE(mean), fp32, synthetic data).
 
-    python bench.py --gpus N --steps K --warmup W [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--dump-outputs DIR]
+
+``ms_per_step`` is the wall time of one of the K timed steps.  ``--dump-outputs DIR`` writes the product of the last
+timed step to ``DIR/ggn_matvec.npy`` (float32): the inputs are seeded, so two builds run with the same arguments can
+be compared output for output.
 
 One "step" = one ``GGNLinearOperator @ v`` over this rank's mini-batch shard (B rows, default 8:
 the HBM-bound regime the north star targets) through the public operator API, followed -- when
@@ -40,10 +44,8 @@ import os
 import sys
 import time
 
-# Round 6: the bench no longer sets GPU_MAX_HW_QUEUES (rounds 3-5 ran with 16): every figure is what a drop-in user of the
-# package gets with the runtime's default of 4 hardware queues.  What 16 queues change (profiles/r06_kfac_capture_rule.txt):
-# the twelve-stream eigensolver leg 101 -> 78 ms, the captured KFAC build 4.25 -> 5.06 ms (the package then captures a
-# one-branch graph, computers._CAPTURE_BRANCHES), the 42 Cholesky inverses 10.9 vs 11.2 ms, the headline matvec nothing.
+# The bench leaves the runtime's hardware-queue count alone: every figure is what a drop-in user of the package gets
+# with the runtime's default of 4 hardware queues, the headline matvec included.
 
 import numpy as np
 import torch
@@ -316,21 +318,6 @@ def secondary_configs(device) -> dict:
                       "wall-time model; orthogonality / residual verified, float64 retry) + eigenvalue-correction sweep; "
                       "eigh_ms / ekfac_total_ms = MEDIAN of 5 calls after one warm-up, [min, max] beside them")
         ek["eigh_policy"] = "native (clo_sytrd_f32 persistent panels -> divide & conquer -> block reflectors)"
-        ek["hip_hw_queues"] = os.environ.get("GPU_MAX_HW_QUEUES", "4 (runtime default)")
-        if os.environ.get("CLO_BENCH_EKFAC_16Q", "1") == "1" and "GPU_MAX_HW_QUEUES" not in os.environ:
-            # the same leg in a child process with 16 hardware queues (the runtime reads the variable at start-up): the
-            # twelve eigensolver streams then get a queue each -- the setting rounds 3-5 benchmarked with
-            import subprocess
-
-            try:
-                env = dict(os.environ, GPU_MAX_HW_QUEUES="16", CLO_BENCH_SKIP="c3,c5", CLO_BENCH_EKFAC_16Q="0")
-                res = subprocess.run([sys.executable, os.path.abspath(__file__), "--secondary-only"], env=env,
-                                     capture_output=True, text=True, timeout=600)
-                sub = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])["c4_ekfac_resnet18"]
-                ek["with_16_hw_queues"] = {k: sub[k] for k in ("eigh_ms", "eigh_ms_min_max", "ekfac_total_ms",
-                                                                "ekfac_total_ms_min_max", "ekfac_matvec_ms")}
-            except Exception as e:  # noqa: BLE001
-                ek["with_16_hw_queues"] = {"error": repr(e)}
         out["c4_ekfac_resnet18"] = ek
         del K, E, facs, model, params
         torch.cuda.empty_cache()
@@ -589,9 +576,14 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--batch", type=int, default=8, help="mini-batch rows per GPU")
     ap.add_argument("--no-extras", action="store_true", help="skip the roofline / cpu_baseline legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the product of the last timed step as DIR/ggn_matvec.npy "
+                         "(float32, [D]; rank 0)")
     ap.add_argument("--secondary-only", action="store_true",
                     help="print only the secondary configurations (C3 / C4-EKFAC / C5; CLO_BENCH_SKIP leaves some out)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.secondary_only:
         torch.cuda.set_device(0)
         print(json.dumps(secondary_configs(torch.device("cuda", 0))))
@@ -689,6 +681,13 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert out is not None and torch.isfinite(out).all()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path received in the last timed step: the (all-reduced) GGN-vector product.  The
+        # model, data and probe vectors are seeded, so the same arguments give the same inputs on every run and build.
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dumped = os.path.join(args.dump_outputs, "ggn_matvec.npy")
+        np.save(dumped, out.detach().float().cpu().numpy())
 
     ms_per_step = 1e3 * elapsed / args.steps
     n_gt1 = None
@@ -747,7 +746,6 @@ def main() -> None:
             "workload": "C2: GGNLinearOperator @ v, MLP 1024-2688-2688-10 (D=10010122), MSE mean, "
                         f"{args.batch} rows per GPU, K=1",
             "rows_per_gpu": args.batch,
-            "hip_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "4 (runtime default; not set by the bench)"),
             "parallelism": (f"dp{world} (data shards + RCCL all-reduce of the [D] result"
                             + (", overlapped with the next product)" if overlap else ")")) if world > 1 else "single GPU",
         },
@@ -755,6 +753,9 @@ def main() -> None:
 
     if n_gt1 is not None:
         result["n_gt1"] = n_gt1
+    if dumped is not None:
+        result["dumped_outputs"] = {"ggn_matvec": {"path": dumped, "shape": [D], "dtype": "float32",
+                                                   "probe_buffer": (args.steps - 1) % nbuf}}
 
     if rank == 0 and world == 1 and not args.no_extras:
         # ---- roofline leg: same steps with per-kernel HIP events on the launch stream
