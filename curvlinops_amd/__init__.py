@@ -2,8 +2,9 @@
 f-dangel/curvlinops, behind the reference's linear-operator API.
 
 Public names mirror ``curvlinops/__init__.py`` for the path in scope:
-curvature operators, KFAC / EKFAC with their structured building blocks, and the probe-packing
-trace estimators.  The compute kernels live in ``csrc/*.hip`` (C ABI in
+curvature operators, KFAC / EKFAC with their structured building blocks, the probe-packing
+trace estimators and the Lanczos spectral densities (Papyan 2020).  The compute kernels live in
+``csrc/*.hip`` (C ABI in
 ``include/curvlinops_amd.h``); importing this package does not need a GPU, running a GPU fp32
 operator does need ``lib/libclo_hip.so`` (build with ``python -m curvlinops_amd.csrc.build``).
 """
@@ -32,6 +33,12 @@ from curvlinops_amd.kronecker import (
     KroneckerProductLinearOperator,
 )
 from curvlinops_amd.linop import PyTorchLinearOperator
+from curvlinops_amd.spectrum import (
+    LanczosApproximateLogSpectrumCached,
+    LanczosApproximateSpectrumCached,
+    lanczos_approximate_log_spectrum,
+    lanczos_approximate_spectrum,
+)
 from curvlinops_amd.trace import (
     hutchinson_diag,
     hutchinson_squared_fro,
@@ -70,4 +77,8 @@ __all__ = [
     "hutchinson_squared_fro",
     "xtrace",
     "xdiag",
+    "lanczos_approximate_spectrum",
+    "lanczos_approximate_log_spectrum",
+    "LanczosApproximateSpectrumCached",
+    "LanczosApproximateLogSpectrumCached",
 ]

@@ -160,6 +160,9 @@ _SIGNATURES = {
     "clo_axpby_f32": (c_int, [_PF, _PF, c_long, c_float, c_float, c_void_p]),
     "clo_dot_ws_bytes": (c_long, []),
     "clo_dot_f32": (c_int, [_PF, _PF, c_long, c_float, _PF, c_void_p, c_void_p]),
+    "clo_lanczos_ws_bytes": (c_long, [c_long, c_int]),
+    "clo_lanczos_step_f32": (c_int, [_PF, _PF, _PF, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, _PF, c_long, c_int, c_void_p, c_void_p]),
     "clo_cg_update_f32": (c_int, [_PF, _PF, _PF, _PF, c_long, _PF, _PF, _PF, c_void_p, c_void_p]),
     "clo_cg_direction_f32": (c_int, [_PF, _PF, c_long, _PF, _PF, c_void_p]),
     "clo_transpose_f32": (c_int, [_PF, _PF, c_long, c_long, c_void_p]),
@@ -1043,6 +1046,51 @@ def dot(x: Tensor, y: Tensor, scale: float = 1.0) -> Tensor:
     ws = torch.empty(lib.clo_dot_ws_bytes(), device=x.device, dtype=torch.uint8)
     _check(lib.clo_dot_f32(_pc(x), _pc(y), x.numel(), scale, _pc(out), ws.data_ptr(), _stream()), "clo_dot_f32")
     return out[0]
+
+
+LANCZOS_FIRST, LANCZOS_LAST = 1, 2
+
+
+def lanczos_ws(D: int, K: int, device) -> Tensor:
+    """Zeroed workspace of ``clo_lanczos_step_f32`` (reusable for every step of chains of this shape on one stream)."""
+    n = int(load().clo_lanczos_ws_bytes(D, K))
+    if n < 0:
+        raise ValueError(f"clo_lanczos_ws_bytes: invalid shape D={D}, K={K}")
+    return torch.zeros(-(-n // 8), device=device, dtype=torch.float64)
+
+
+def _pd(t: Tensor | None) -> int | None:
+    """Device address of a float64 GPU tensor (scalars of the Lanczos step); None passes NULL."""
+    if t is None:
+        return None
+    if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+        raise ValueError(f"expected a contiguous float64 GPU tensor, got {t.dtype} on {t.device}")
+    return t.data_ptr()
+
+
+def lanczos_step(W: Tensor, U: Tensor, P: Tensor | None, s_cur: Tensor, s_prev: Tensor | None, beta_prev: Tensor | None,
+                 alpha: Tensor, beta: Tensor, s_next: Tensor, ws: Tensor, *, first: bool, last: bool,
+                 out: Tensor | None = None) -> None:
+    """One Lanczos step of ``K`` chains on ``[D, K]`` fp32 blocks (``clo_lanczos_step_f32``): ``W = A U`` of the stored
+    (unnormalised, scale ``s_cur``) block ``U``; ``P`` holds the previous block (scale ``s_prev``) and receives the
+    unnormalised next one.  ``alpha`` / ``beta`` / ``s_next`` are ``[K]`` float64 device outputs; ``out`` (``[D, >= K]``
+    view with unit column stride) receives the normalised ``U``."""
+    D, K = U.shape
+    if W.shape != U.shape or (P is not None and P.shape != U.shape):
+        raise ValueError("lanczos_step shape mismatch")
+    for t in (s_cur, alpha, beta, s_next) + (() if first else (s_prev, beta_prev)):
+        if t.numel() != K:
+            raise ValueError("lanczos_step: per-column scalars must have K entries")
+    ldo = 0
+    if out is not None:
+        if out.shape[0] != D or out.shape[1] < K or (out.shape[1] > 1 and out.stride(1) != 1):
+            raise ValueError("lanczos_step: out must be a [D, >= K] view with unit column stride")
+        ldo = out.stride(0) if D > 1 else max(out.shape[1], K)
+    flags = (LANCZOS_FIRST if first else 0) | (LANCZOS_LAST if last else 0)
+    rc = load().clo_lanczos_step_f32(_pc(W), _pc(U), _pc(P), D, K, _pd(s_cur), None if first else _pd(s_prev),
+                                     None if first else _pd(beta_prev), _pd(alpha), _pd(beta), _pd(s_next), _p(out),
+                                     ldo, flags, ws.data_ptr(), _stream())
+    _check(rc, "clo_lanczos_step_f32")
 
 
 def transpose(x: Tensor) -> Tensor:

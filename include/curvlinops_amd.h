@@ -408,6 +408,21 @@ int clo_cg_update_f32(float *x, float *r, const float *p, const float *ap, long 
 int clo_cg_direction_f32(float *p, const float *z, long n, const float *num, const float *den,
                          void *stream);
 
+/* One three-term Lanczos step for K independent chains (curvlinops_amd/spectrum.py; csrc/lanczos.hip), blocks [D][K]
+ * (K trailing, contiguous, 1 <= K <= 64, 64-bit indexing).  Blocks are stored UNNORMALISED with per-column FLOAT64 device
+ * scales (v = s u); W = A U is the operator product of the stored current block U.  Per column k:
+ *   w = s_cur W - beta_prev s_prev P            (P = previous block; the second term is skipped with flags & 1, step 0)
+ *   alpha[k] = <w, s_cur U>;   w -= alpha[k] s_cur U;   beta[k] = ||w||;   s_next[k] = 1 / beta[k]
+ *   P <- w                                      (unnormalised next block; skipped with flags & 2, the last step)
+ *   out[i * ldo + k] = s_cur[k] U[i][k]         (optional strided copy of the normalised current block; out may be NULL)
+ * Two launches, 28 D K bytes; float64 accumulation, fixed-order partials, bit-identical on repeat.  ws:
+ * clo_lanczos_ws_bytes(D, K) bytes of device memory, ZEROED before its first use (the kernels leave it ready for the
+ * next call); one workspace serves one stream at a time. */
+long clo_lanczos_ws_bytes(long D, int K);
+int clo_lanczos_step_f32(const float *W, const float *U, float *P, long D, int K, const double *s_cur,
+                         const double *s_prev, const double *beta_prev, double *alpha, double *beta, double *s_next,
+                         float *out, long ldo, int flags, void *ws, void *stream);
+
 /* ---- symmetric eigensolver behind clo_sytrd_f32 (csrc/eigh.hip; replaces rocSOLVER sstedc / sormtr behind
  * torch.linalg.eigh at computers/_base.py:355-372, kronecker.py:292-300): the building blocks that clo_eigh_f32
  * composes (rounds 2-3 drove them level by level from curvlinops_amd/eigh_native.py); every O(n^3) product is a
