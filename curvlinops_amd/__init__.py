@@ -3,7 +3,8 @@ f-dangel/curvlinops, behind the reference's linear-operator API.
 
 Public names mirror ``curvlinops/__init__.py`` for the path in scope:
 curvature operators, KFAC / EKFAC with their structured building blocks, the probe-packing
-trace estimators and the Lanczos spectral densities (Papyan 2020).  The compute kernels live in
+trace estimators, the Lanczos spectral densities (Papyan 2020) and a device-resident top-k eigensolver
+(``eigsh``, block Lanczos with thick restart).  The compute kernels live in
 ``csrc/*.hip`` (C ABI in
 ``include/curvlinops_amd.h``); importing this package does not need a GPU, running a GPU fp32
 operator does need ``lib/libclo_hip.so`` (build with ``python -m curvlinops_amd.csrc.build``).
@@ -17,6 +18,7 @@ from curvlinops_amd.curvature import (
     HessianLinearOperator,
 )
 from curvlinops_amd.diag import DiagonalLinearOperator
+from curvlinops_amd.eigensolver import eigsh
 from curvlinops_amd.enums import FisherType, KFACType
 from curvlinops_amd.ggn_diagonal import GGNDiagonalLinearOperator
 from curvlinops_amd.inverse import (
@@ -81,4 +83,5 @@ __all__ = [
     "lanczos_approximate_log_spectrum",
     "LanczosApproximateSpectrumCached",
     "LanczosApproximateLogSpectrumCached",
+    "eigsh",
 ]

@@ -163,6 +163,11 @@ _SIGNATURES = {
     "clo_lanczos_ws_bytes": (c_long, [c_long, c_int]),
     "clo_lanczos_step_f32": (c_int, [_PF, _PF, _PF, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, _PF, c_long, c_int, c_void_p, c_void_p]),
+    "clo_basis_ws_bytes": (c_long, [c_long, c_int, c_int]),
+    "clo_basis_project_f64": (c_int, [c_void_p, c_long, _PF, c_long, c_int, _PF, c_long, c_int, c_long, c_void_p, c_void_p]),
+    "clo_basis_update_f32": (c_int, [_PF, c_long, _PF, c_long, c_int, c_void_p, c_long, c_int, c_void_p, c_long, c_long,
+                                     c_void_p, c_void_p]),
+    "clo_basis_combine_f32": (c_int, [_PF, c_long, _PF, c_long, c_int, c_void_p, c_long, c_int, c_long, c_void_p]),
     "clo_cg_update_f32": (c_int, [_PF, _PF, _PF, _PF, c_long, _PF, _PF, _PF, c_void_p, c_void_p]),
     "clo_cg_direction_f32": (c_int, [_PF, _PF, c_long, _PF, _PF, c_void_p]),
     "clo_transpose_f32": (c_int, [_PF, _PF, c_long, c_long, c_void_p]),
@@ -1091,6 +1096,70 @@ def lanczos_step(W: Tensor, U: Tensor, P: Tensor | None, s_cur: Tensor, s_prev: 
                                      None if first else _pd(beta_prev), _pd(alpha), _pd(beta), _pd(s_next), _p(out),
                                      ldo, flags, ws.data_ptr(), _stream())
     _check(rc, "clo_lanczos_step_f32")
+
+
+def _rows(t: Tensor, name: str) -> tuple[int, int, int]:
+    """``(rows, cols, leading dimension)`` of a 2-D view with unit column stride (the basis kernels' row-major operands)."""
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{name} must be a 2-D view with unit column stride")
+    rows, cols = t.shape
+    return rows, cols, t.stride(0) if rows > 1 else cols
+
+
+def basis_ws(D: int, m: int, b: int, device) -> Tensor:
+    """Workspace of ``clo_basis_project_f64`` / ``clo_basis_update_f32`` for a ``[D, <= m]`` basis and ``[D, <= b]`` blocks."""
+    n = int(load().clo_basis_ws_bytes(D, m, b))
+    if n <= 0:
+        raise ValueError(f"clo_basis_ws_bytes: invalid shape D={D}, m={m}, b={b}")
+    return torch.empty(-(-n // 8), device=device, dtype=torch.float64)
+
+
+def basis_project(Q: Tensor, W: Tensor, ws: Tensor | None = None, out: Tensor | None = None) -> Tensor:
+    """``Q^T W`` as a float64 ``[m, b]`` tensor for float32 ``Q [D, m]`` (m <= 1024) and ``W [D, b]`` (b <= 64): one pass
+    over ``Q``, exact products, float64 accumulation (``clo_basis_project_f64``)."""
+    D, m, ldq = _rows(Q, "Q")
+    Dw, b, ldw = _rows(W, "W")
+    if Dw != D:
+        raise ValueError("basis_project: Q and W must have the same rows")
+    if out is None:
+        out = torch.empty(m, b, device=Q.device, dtype=torch.float64)
+    ws = basis_ws(D, m, b, Q.device) if ws is None else ws
+    rc = load().clo_basis_project_f64(_pd(out), b, _p(Q), ldq, m, _p(W), ldw, b, D, ws.data_ptr(), _stream())
+    _check(rc, "clo_basis_project_f64")
+    return out
+
+
+def basis_update(W: Tensor, Q: Tensor, C: Tensor, ws: Tensor | None = None, reproject: bool = False) -> Tensor | None:
+    """``W -= Q C`` in place for float32 ``Q [D, m]``, ``W [D, b]`` and float64 ``C [m, b]`` (``clo_basis_update_f32``).
+    ``reproject=True`` also returns ``Q^T W_new`` (float64 ``[m, b]``) from the same pass over ``Q``."""
+    D, m, ldq = _rows(Q, "Q")
+    Dw, b, ldw = _rows(W, "W")
+    if Dw != D or tuple(C.shape) != (m, b):
+        raise ValueError("basis_update shape mismatch")
+    C2 = torch.empty(m, b, device=Q.device, dtype=torch.float64) if reproject else None
+    if reproject and ws is None:
+        ws = basis_ws(D, m, b, Q.device)
+    rc = load().clo_basis_update_f32(_p(W), ldw, _p(Q), ldq, m, _pd(C), b, b, _pd(C2), b, D,
+                                     None if ws is None else ws.data_ptr(), _stream())
+    _check(rc, "clo_basis_update_f32")
+    return C2
+
+
+def basis_combine(Q: Tensor, S: Tensor, out: Tensor | None = None) -> Tensor:
+    """``Q S`` (float32 ``[D, p]``) for float32 ``Q [D, m]`` and float64 ``S [m, p]`` (m, p <= 1024), out of place
+    (``clo_basis_combine_f32``)."""
+    D, m, ldq = _rows(Q, "Q")
+    if S.shape[0] != m:
+        raise ValueError("basis_combine shape mismatch")
+    p = S.shape[1]
+    if out is None:
+        out = torch.empty(D, p, device=Q.device, dtype=torch.float32)
+    Do, po, ldy = _rows(out, "out")
+    if (Do, po) != (D, p):
+        raise ValueError("basis_combine: out must be [D, p]")
+    rc = load().clo_basis_combine_f32(_p(out), ldy, _p(Q), ldq, m, _pd(S), p, p, D, _stream())
+    _check(rc, "clo_basis_combine_f32")
+    return out
 
 
 def transpose(x: Tensor) -> Tensor:

@@ -423,6 +423,24 @@ int clo_lanczos_step_f32(const float *W, const float *U, float *P, long D, int K
                          const double *s_prev, const double *beta_prev, double *alpha, double *beta, double *s_next,
                          float *out, long ldo, int flags, void *ws, void *stream);
 
+/* Wide Krylov bases of the block eigensolver (curvlinops_amd/eigensolver.py; csrc/basis.hip): float32 Q [D][ldq] with
+ * 1 <= m <= 1024 columns, blocks W [D][ldw] with 1 <= b <= 64 columns, any leading dimensions, 64-bit row indexing.
+ *   clo_basis_project_f64  C [m][ldc] (FLOAT64) = Q^T W; exact products, float64 accumulation; one pass over Q, W read
+ *                          once per 64-column tile of Q.  4 D (m + ceil(m / 64) b) bytes.
+ *   clo_basis_update_f32   W <- W - Q C (C float64 [m][ldc], rounded to float32); with C2 != NULL the same pass also
+ *                          forms C2 [m][ldc2] (FLOAT64) = Q^T W_new.  4 D (ceil(b / 16) m + 2 b) bytes.
+ *   clo_basis_combine_f32  Y [D][ldy] = Q S, S float64 [m][lds] with 1 <= p <= 1024 columns, out of place (no ws).
+ * ws: clo_basis_ws_bytes(D, m, b) bytes, enough for every call with at most m basis and b block columns (per-block
+ * float64 partials, summed in a fixed order: bit-identical on repeat).
+ * D = 0 gives C = 0 / C2 = 0 and touches no row.  No call synchronises the device. */
+long clo_basis_ws_bytes(long D, int m, int b);
+int clo_basis_project_f64(double *C, long ldc, const float *Q, long ldq, int m, const float *W, long ldw, int b, long D,
+                          void *ws, void *stream);
+int clo_basis_update_f32(float *W, long ldw, const float *Q, long ldq, int m, const double *C, long ldc, int b,
+                         double *C2, long ldc2, long D, void *ws, void *stream);
+int clo_basis_combine_f32(float *Y, long ldy, const float *Q, long ldq, int m, const double *S, long lds, int p, long D,
+                          void *stream);
+
 /* ---- symmetric eigensolver behind clo_sytrd_f32 (csrc/eigh.hip; replaces rocSOLVER sstedc / sormtr behind
  * torch.linalg.eigh at computers/_base.py:355-372, kronecker.py:292-300): the building blocks that clo_eigh_f32
  * composes (rounds 2-3 drove them level by level from curvlinops_amd/eigh_native.py); every O(n^3) product is a
