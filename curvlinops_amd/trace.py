@@ -30,28 +30,45 @@ def frobenius_inner(X: Tensor, Y: Tensor) -> Tensor:
 
 _GRAM_MIN_ELEMS = 2**22  # above this, fp32 GPU blocks use the GEMM-rich Gram route
 
+_BASIS_COLS = 1024   # widest basis of clo_basis_project_f64 / clo_basis_update_f32 / clo_basis_combine_f32 (basis.hip)
+_PANEL_COLS = 64     # widest block W of clo_basis_project_f64 / clo_basis_update_f32, and of the tall Gram / apply kernels
+
 
 def _gram64(X: Tensor) -> Tensor:
-    """``X^T X`` in float64 (exact products, float64 accumulation) for a tall float32 GPU block."""
+    """``X^T X`` in float64 (exact products, float64 accumulation) for a tall float32 GPU block of any width: one
+    ``clo_tall_gram_f64`` pass up to 64 columns; wider, the upper block triangle from 64-column panels
+    (``clo_basis_project_f64`` of ``X[:, :j + 64]`` against the panel ``X[:, j:j + 64]``, in 1024-column windows),
+    mirrored so the result is exactly symmetric.  That is about n / 64 passes over ``X`` instead of one."""
     if _hip.tall_gram_supported(X):
         return _hip.tall_gram(X)
-    gram = torch.empty(X.shape[1], X.shape[1], device=X.device, dtype=torch.float32)   # wider than 64 columns
-    _hip.syrk_accum(gram, X, alpha=1.0, beta=0.0)
-    return gram.double()
+    m, n = X.shape
+    upper = torch.zeros(n, n, device=X.device, dtype=torch.float64)
+    ws = _hip.basis_ws(m, min(n, _BASIS_COLS), _PANEL_COLS, X.device)
+    for j in range(0, n, _PANEL_COLS):
+        j1 = min(j + _PANEL_COLS, n)
+        for i in range(0, j1, _BASIS_COLS):
+            i1 = min(i + _BASIS_COLS, j1)
+            upper[i:i1, j:j1] = _hip.basis_project(X[:, i:i1], X[:, j:j1], ws)
+    upper = upper.triu()
+    return upper + upper.triu(1).T
 
 
 def _times_small(X: Tensor, T: Tensor) -> Tensor:
-    """``X T`` for a tall block and a small square ``T`` (float64 in, rounded once)."""
+    """``X T`` for a tall block and a small ``T`` (float64 in, rounded to float32 once in the kernel)."""
     T32 = T.float().contiguous()
     if _hip.tall_apply_supported(X, T32):
         return _hip.tall_apply(X, T32)
+    if max(X.shape[1], T.shape[1]) > _PANEL_COLS and max(X.shape[1], T.shape[1]) <= _BASIS_COLS:
+        return _hip.basis_combine(X, T.double().contiguous())
     return _hip.gemm(X, T32)
 
 
 def project_out(Q: Tensor, G: Tensor) -> Tensor:
     """``G - Q (Q^T G)`` (reference ``meyer2020hutch.py:97-99``): on float32 GPU blocks two streaming passes --
     ``clo_tall_gram_f64`` for the coefficients (float64 accumulation over the 1e7 ... 1e8 rows), ``clo_tall_apply_f32`` for
-    the update -- instead of two library GEMMs with a [D, N] temporary between them."""
+    the update -- instead of two library GEMMs with a [D, N] temporary between them.  Wider than 64 columns, a copy of
+    ``G`` is updated per 64-column panel: float64 coefficients ``clo_basis_project_f64``, then ``clo_basis_update_f32``
+    (per 1024-column window of ``Q``, one after the other).  ``G`` itself is never modified."""
     if _hip.tall_gram_supported(Q, G):
         if Q.shape[1] % 4:   # (the update kernel reads Q in 16-byte pieces: zero columns change nothing)
             Qp = Q.new_zeros(Q.shape[0], -(-Q.shape[1] // 4) * 4)
@@ -60,10 +77,21 @@ def project_out(Q: Tensor, G: Tensor) -> Tensor:
         C = _hip.tall_gram(Q, G).neg_().float().contiguous()
         if _hip.tall_apply_supported(Q, C, G):
             return _hip.tall_apply(Q, C, G, beta=1.0)
+    elif (_hip.is_f32_gpu(Q) and _hip.is_f32_gpu(G) and Q.dim() == 2 and G.dim() == 2 and Q.shape[0] == G.shape[0]
+          and Q.device == G.device and Q.shape[1] >= 1 and G.shape[1] >= 1 and (Q.shape[1] == 1 or Q.stride(1) == 1)):
+        out = G.clone(memory_format=torch.contiguous_format)
+        ws = _hip.basis_ws(Q.shape[0], min(Q.shape[1], _BASIS_COLS), min(G.shape[1], _PANEL_COLS), Q.device)
+        for j in range(0, G.shape[1], _PANEL_COLS):
+            panel = out[:, j:j + _PANEL_COLS]
+            for i in range(0, Q.shape[1], _BASIS_COLS):
+                Qi = Q[:, i:i + _BASIS_COLS]
+                _hip.basis_update(panel, Qi, _hip.basis_project(Qi, panel, ws), ws)
+        return out
     return G - Q @ (Q.T @ G)
 
 
-# Relative eigenvalue of the float64 Gram matrix below which a direction of the block is numerically DEPENDENT: sigma below
+# Relative eigenvalue of the float64 Gram matrix (`_gram64`: float64 at every width -- one tall-Gram pass up to 64 columns,
+# 64-column panels of the basis kernels above) below which a direction of the block is numerically DEPENDENT: sigma below
 # 3e-6 of the largest singular value is inside the rounding noise of a float32 block that came out of an operator product
 # (~1e-6 sigma_max after the O(D) float32 accumulations) -- exact rank deficiency (repeated / zero columns, a rank-8 operator
 # sketched with 32 probes) sits at 1e-14.  Such directions are not range information: `orthonormal_basis` replaces them by
@@ -73,20 +101,27 @@ def project_out(Q: Tensor, G: Tensor) -> Tensor:
 _RANK_TOL = 1e-11
 
 
-def _gram_orthonormal_basis(X: Tensor, complete: bool = True) -> Tensor:
+_ORTHO_TOL = 1e-5      # max |Q^T Q - I| the Gram route must reach; otherwise float64 Householder QR takes over
+_COMPLETION_DEPTH = 2  # nested completions of a rank-deficient basis (the random fill is full rank: one is the norm)
+
+
+def _gram_orthonormal_basis(X: Tensor, complete: bool = True, _depth: int = 0) -> Tensor:
     """Orthonormal basis with ALL ``n`` columns (as the reference's Householder ``Q``, ``meyer2020hutch.py:89-93``) of a very
     tall float32 GPU block from two Gram passes: ``Q = X V diag(lambda)^-1/2`` with ``X^T X = V diag(lambda) V^T``, then
     once more on ``Q`` to push the loss of orthogonality to eps.  The Gram matrices are accumulated in FLOAT64 from exact
-    products (``clo_tall_gram_f64``), so directions are resolved down to the rounding noise of the float32 data
+    products (:func:`_gram64`, at every width), so directions are resolved down to the rounding noise of the float32 data
     (sigma / sigma_max ~ 1e-7) -- a float32 Gram matrix loses everything below sqrt(eps) ~ 3e-3, and round 5 dropped
     those directions from the basis, which made the estimator differ from the reference's on decaying spectra.
     Directions that are exactly dependent (relative eigenvalue < 1e-13) are replaced by random directions orthogonalised
     against the rest: Householder QR also returns n orthonormal columns for a rank-deficient block, and Hutch++ is exact
     for any orthonormal basis that contains range(X).  Everything O(m) is a streaming kernel (Householder QR of an
-    [85M, 32] block takes seconds in the vendor solver, this takes tens of milliseconds)."""
+    [85M, 32] block takes seconds in the vendor solver, this takes tens of milliseconds).  If no pass saw a well
+    conditioned input within four passes, ``Q^T Q`` is checked once more and, off by more than 1e-5, ``Q`` is
+    re-orthonormalised by float64 Householder QR (same columns, same range)."""
     Q = X if X.is_contiguous() else X.contiguous()
     n = Q.shape[1]
     missing = 0
+    settled = False
     for it in range(4):
         gram = _gram64(Q)
         # (normalised: rocSOLVER's tridiagonal solver applies an absolute tolerance, linalg_native._unit_scale)
@@ -105,16 +140,24 @@ def _gram_orthonormal_basis(X: Tensor, complete: bool = True) -> Tensor:
         # well conditioned has produced an orthonormal block (two passes for any sketch that is not nearly singular,
         # a third for spectra that reach the float32 noise floor)
         if it >= 1 and float(lam[keep].min() / lam.max()) > 0.25:
+            settled = True
             break
+    if not settled and Q.shape[1]:
+        eye = torch.eye(Q.shape[1], device=Q.device, dtype=torch.float64)
+        if float((_gram64(Q) - eye).abs().max()) > _ORTHO_TOL:
+            Q = orthonormal_basis(Q.double()).to(X.dtype)
     if not complete and Q.shape[1] == 0:
         return torch.zeros(X.shape[0], 1, device=X.device, dtype=X.dtype)   # (a zero block: one zero column, no range)
     if missing and complete:
         # complete the basis: random directions, twice projected off range(Q), orthonormalised among themselves
+        if _depth >= _COMPLETION_DEPTH:
+            raise RuntimeError(f"orthonormal_basis: the random completion of {missing} columns is rank-deficient "
+                               f"{_depth} times in a row")
         R = torch.randn(X.shape[0], missing, device=X.device, dtype=X.dtype)
         if Q.shape[1]:
             for _ in range(2):
                 R = project_out(Q, R)
-        R = _gram_orthonormal_basis(R.contiguous())
+        R = _gram_orthonormal_basis(R.contiguous(), True, _depth + 1)
         Q = torch.cat([Q, R], dim=1) if Q.shape[1] else R
     return Q
 
@@ -124,9 +167,10 @@ def _gram_qr(X: Tensor) -> tuple[Tensor, Tensor] | None:
     XTrace / XDiag need (``trace/epperly2024xtrace.py:52-60`` call ``torch.linalg.qr``, which is rocSOLVER on this
     platform).  Their leave-one-out vectors ``s_i`` are the directions of ``T^-T e_i``: the complement of
     ``range(X[:, != i])`` inside ``range(Q)`` whatever the shape of ``T``, so ``T`` need not be triangular.  Two Gram
-    passes (``clo_tall_gram_f64``: float64 accumulation; ``clo_tall_apply_f32``), the two small eigenproblems in float64;
-    ``T = (L2^1/2 V2^T)(L1^1/2 V1^T)`` is inverted in closed form.  None if ``X`` is numerically rank-deficient (the
-    caller then takes the float64 route)."""
+    passes (:func:`_gram64`: float64 accumulation at every width; :func:`_times_small`), the two small eigenproblems in
+    float64; ``T = (L2^1/2 V2^T)(L1^1/2 V1^T)`` is inverted in closed form.  None if ``X`` is numerically rank-deficient,
+    or if the second pass did not see a well-conditioned input, so ``Q`` would not be orthonormal (the caller then takes
+    the float64 route)."""
     Q = X if X.is_contiguous() else X.contiguous()
     n = Q.shape[1]
     Tinv = torch.eye(n, device=X.device, dtype=torch.float64)
@@ -135,7 +179,7 @@ def _gram_qr(X: Tensor) -> tuple[Tensor, Tensor] | None:
         gscale = gram.abs().amax().clamp_min(torch.finfo(torch.float32).tiny)
         lam, V = torch.linalg.eigh(gram / gscale)
         lam = lam * gscale
-        if not bool((lam > lam.max() * (1e-10 if it == 0 else 1e-12)).all()):
+        if not bool((lam > lam.max() * (1e-10 if it == 0 else 0.25)).all()):
             return None
         step = V / lam.sqrt()                      # X_it = X_{it+1} (L^1/2 V^T)  =>  X_{it+1} = X_it (V L^-1/2)
         Q = _times_small(Q, step)
