@@ -647,9 +647,6 @@ __global__ __launch_bounds__(WVM * WVN * 64, 2) void gemm_v2_kernel(const GemmAr
   const float alpha = to_ws ? 1.f : p.alpha;
   const float beta = to_ws ? 0.f : p.beta;
   const bool mirror = p.sym && !to_ws && bm != bn;
-#ifndef CLO_V2_WIDE_EPI
-#define CLO_V2_WIDE_EPI 1
-#endif
   // Wide form (round 6, as in gemm_v3.hip): the tile is staged in LDS (the loop's buffers are dead behind its last barrier; the
   // launch sizes the allocation for the larger of the two uses) and leaves as full-row 16-byte stores, its mirror image
   // likewise; the separate destination of the last column (col_out) is served from the staged tile.
@@ -657,7 +654,7 @@ __global__ __launch_bounds__(WVM * WVN * 64, 2) void gemm_v2_kernel(const GemmAr
   E.kind = to_ws ? EPI_NONE : p.epi;
   E.act = p.e_act; E.div = p.e_div; E.vec = p.e_vec; E.mul = p.e_mul; E.ld_mul = p.ld_mul; E.out2 = p.e_out2; E.Cbase = p.C;
   const bool has_col_out = !to_ws && p.col_out;
-  const bool wide = CLO_V2_WIDE_EPI && (ldc & 3) == 0 && ((unsigned long)C & 15ul) == 0 &&
+  const bool wide = (ldc & 3) == 0 && ((unsigned long)C & 15ul) == 0 &&
                     (E.kind == EPI_NONE || (!mirror && !has_col_out && (E.kind != EPI_ACT || ((unsigned long)E.out2 & 15ul) == 0)));
   if (wide) {
     constexpr int NTHR = NW * 64, PD = BNt + 4, PM = BMt + 4;
@@ -934,10 +931,7 @@ static int pick_mode(const float *P, long so, long sk, long sbatch, int batch) {
 struct V2Config { int bm, bn, bk; };
 static V2Config v2_config(int M, int N, int K, long batch, int sym, bool allow_small = true) {
   // (few-row problems keep their 32- / 64-row tiles unless they are tiny)
-#ifndef CLO_GEMM_SMALL_MAX
-#define CLO_GEMM_SMALL_MAX (1024L * 1024L)
-#endif
-  static const long small_max = CLO_GEMM_SMALL_MAX;
+  constexpr long small_max = 1024L * 1024L;
   // (a batch of skinny products -- the panels and column updates of the batched Cholesky chain, N <= 128 -- is judged by
   // ONE matrix: 3 x (4480 x 128) on 128 x 128 x 32 tiles is 105 workgroups with k loops of up to 32 steps, 50-110 us per
   // product on the critical path; on 64 x 64 x 64 tiles 8-15 us)
@@ -952,10 +946,6 @@ static V2Config v2_config(int M, int N, int K, long batch, int sym, bool allow_s
 // v2 needs float4-complete operands: 16-byte aligned, K % 4 == 0 for k-contiguous operands, the
 // outer extent in memory % 4 == 0 for outer-contiguous ones.
 bool gemm_v2_eligible(const GemmArgs &a, int batch) {
-#ifndef CLO_GEMM_V1
-#define CLO_GEMM_V1 0
-#endif
-  static const int v2_off = CLO_GEMM_V1;
   const int ma = pick_mode(a.A, a.sa_m, a.sa_k, a.sa_b, batch);
   const int mb = pick_mode(a.B, a.sb_n, a.sb_k, a.sb_b, batch);
   const bool a_vec = ma == MODE_OC_VEC || ma == MODE_KC_VEC;
@@ -966,7 +956,7 @@ bool gemm_v2_eligible(const GemmArgs &a, int batch) {
   if (a.ones && (a_kc || b_kc)) return false;  // the ones column lives in the outer-contiguous loader
   if (a.ones_b && b_kc) return false;
   const int Mr = a.M - a.ones, Nr = a.N - (a.ones | a.ones_b);   // extents that exist in memory
-  return !v2_off && a_vec && b_vec && a.K > 0 &&
+  return a_vec && b_vec && a.K > 0 &&
          (a_kc ? (a.K % 4 == 0 && Kc % 4 == 0) : (Mr % 4 == 0 && Mr >= 4)) &&
          (b_kc ? (a.K % 4 == 0 && Kc % 4 == 0) : (Nr % 4 == 0 && Nr >= 4));
 }
@@ -1052,13 +1042,11 @@ int launch_gemm(GemmArgs a, int batch, hipStream_t stream) {
   else if (b_kc) CLO_V2(false, true, BKV, BMV, BNV, WM_, WN_)           \
   else CLO_V2(false, false, BKV, BMV, BNV, WM_, WN_)
     const long nblocks = (long)grid.x * grid.y;
-#ifndef CLO_GEMM_V3_MIN_K
-#define CLO_GEMM_V3_MIN_K 129
-#endif
+    constexpr int v3_min_k = 129;
     // (K <= 128 is four k tiles: the LDS-DMA ring of the v3 engine is barely full before it drains, the register-staged loop
     // below wins -- 2688 x 2688 x 128: 34.8 -> 28.4 us, 2304 x 2304 x 128: 33.7 -> 30.3, 2688 x 1024 x 128: 21.8 -> 18.3; at
     // K = 256 the engine is ahead again, 41.2 vs 44.8 us)
-    const bool v3_deep = a.K >= CLO_GEMM_V3_MIN_K || cfg.bk == 64;
+    const bool v3_deep = a.K >= v3_min_k || cfg.bk == 64;
     if (v3_deep && ((cfg.bm == 128 && cfg.bk == 32) || (cfg.bk == 64 && gemm_v3_small(a, batch))) && gemm_v3_eligible(a, batch)) {
       if (cfg.bk == 64) {   // (the LDS-DMA engine's k tiles are 32 deep)
         a.k_per_split = (int)cdiv(cdiv(a.K, a.splitk), 32) * 32;
@@ -1128,11 +1116,7 @@ int launch_gemm_sqsum(GemmArgs a, int batch, int splits, hipStream_t stream) {
   // = odd wide)
   GemmArgs e = a;
   if (a.n_mem) e.N = a.n_mem;
-#ifndef CLO_GEMM_SQSUM_V2
-#define CLO_GEMM_SQSUM_V2 1
-#endif
-  static const int sq_v2 = CLO_GEMM_SQSUM_V2;
-  if (sq_v2 && (a.n_mem == 0 || (a.n_mem % 4 == 0 && a.n_mem >= a.N && a.sb_n == 1)) && gemm_v2_eligible(e, batch)) {
+  if ((a.n_mem == 0 || (a.n_mem % 4 == 0 && a.n_mem >= a.N && a.sb_n == 1)) && gemm_v2_eligible(e, batch)) {
     const bool a_kc = a.mode_a == MODE_KC_VEC, b_kc = a.mode_b == MODE_KC_VEC;
 #define CLO_SQ(AK, BKC_)                                                                                          \
   {                                                                                                               \
@@ -1423,15 +1407,9 @@ int launch_mlp_fwd3(const float *A, const float *dA, const float *W, const float
   const bool tiny = (long)N * d_out <= 256L * 256L && d_in <= 1024;
   // (round 6: 64-row tiles also where they pad less than 128-row tiles -- 129 ... 192 rows are three tiles of 64 instead of two of
   // 128, the second mostly padding: the 128 -> 129-row step of the matvec was 180 -> 257 us)
-#ifndef CLO_FWD3_PAD64
-#define CLO_FWD3_PAD64 1
-#endif
   // (measured: 129 / 160 / 192 rows 267 -> 245 / 261 -> 243 / 276 -> 258 us; 257 ... 320 rows LOSE 23 us with five 64-row tiles)
-  const bool pad64 = CLO_FWD3_PAD64 && N > 128 && N <= 192;
-#ifndef CLO_FWD3_PAD32
-#define CLO_FWD3_PAD32 1
-#endif
-  const bool pad32 = CLO_FWD3_PAD32 && N > 64 && N <= 96;   // (three 32-row tiles instead of one 128-row tile that is a third padding)
+  const bool pad64 = N > 128 && N <= 192;
+  const bool pad32 = N > 64 && N <= 96;   // (three 32-row tiles instead of one 128-row tile that is a third padding)
   const int bm = tiny ? 32 : (N <= 32 || pad32 ? 32 : (N <= 64 || pad64 ? 64 : 128));
   const int bn = tiny ? 64 : (bm == 128 ? 64 : 128);
   const int bk = tiny ? 64 : 16;

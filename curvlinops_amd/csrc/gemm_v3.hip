@@ -197,7 +197,8 @@ __device__ __forceinline__ void v3_tile(const GemmArgs &p, long lin, int y, bool
 // LDS ring of its own, run the k loop on one half of the tile's k range each and meet at the same barrier once per k tile;
 // group 1 hands its accumulators to group 0 through LDS at the end.  A SIMD then holds two waves of DIFFERENT rings: while one
 // is parked at its s_waitcnt / barrier the other issues MFMAs (the four-wave 64 x 64 loop sat parked 39 % of its wave cycles,
-// SQ_WAIT_ANY, profiles/r05_gemm_midsize_sweep.txt), and a tile's k loop is half as long.
+// SQ_WAIT_ANY, profiles/r05_gemm_midsize_sweep.txt), and a tile's k loop is half as long.  Measured 10 - 25 % slower
+// (profiles/r06_gemm_kgroup_ab.txt) and no longer launched: every instance is KG = 1.
 template <bool AKC, bool BKC, int BMt, int BNt, int WVM, int WVN, int NST, bool SK, int KG = 1>
 __global__ __launch_bounds__(WVM *WVN * 64 * KG) void gemm_v3_kernel(const GemmArgs p, const V3Sched s) {
   static_assert(KG == 1 || !SK, "the k-group form has no stream-K schedule");
@@ -547,9 +548,6 @@ __global__ __launch_bounds__(WVM *WVN * 64 * KG) void gemm_v3_kernel(const GemmA
         const float alpha = to_ws ? 1.f : pf->alpha;
         const float beta = to_ws ? 0.f : pf->beta;
         const bool mirror = pf->sym && !to_ws && ct.bm != ct.bn;
-#ifndef CLO_V3_WIDE_EPI
-#define CLO_V3_WIDE_EPI 1
-#endif
         // Wide form: when this was the workgroup's last unit the ring is dead, and the tile (then its mirror image) is staged in
         // it and leaves as full-row 16-byte stores.  The per-lane form below wrote 32 four-byte lanes per row segment -- 256
         // store instructions per 128 x 128 tile, 4.7 - 5.6 us between the last MFMA and the end of the kernel -- and the mirror image
@@ -558,7 +556,7 @@ __global__ __launch_bounds__(WVM *WVN * 64 * KG) void gemm_v3_kernel(const GemmA
         E.kind = to_ws ? EPI_NONE : pf->epi;
         E.act = pf->e_act; E.div = pf->e_div; E.vec = pf->e_vec; E.mul = pf->e_mul; E.ld_mul = pf->ld_mul; E.out2 = pf->e_out2;
         E.Cbase = pf->C;
-        const bool wide = CLO_V3_WIDE_EPI && KG == 1 && u + 1 == n_units && (ldc & 3) == 0 && ((unsigned long)C & 15ul) == 0 &&
+        const bool wide = KG == 1 && u + 1 == n_units && (ldc & 3) == 0 && ((unsigned long)C & 15ul) == 0 &&
                           (E.kind == EPI_NONE || (!mirror && (E.kind != EPI_ACT || ((unsigned long)E.out2 & 15ul) == 0)));
         if (wide) {
           const int Mx = pf->M, Nx = pf->N;
@@ -675,18 +673,11 @@ static long v3_streamk_workers(long tiles, int K) {
   // at least two k tiles per worker: a shorter range is all pipeline fill
   workers = std::max<long>(1, std::min<long>(workers, units / 2));
   if (workers <= tiles && tiles <= kNumCU) return 0;   // nothing to split: one tile per workgroup
-#ifdef CLO_V3_SK_WORKERS   // (experiments: a fixed number of stream-K workers)
-  workers = std::max<long>(1, std::min<long>(CLO_V3_SK_WORKERS, std::min<long>(units, kNumCU)));
-#endif
   return workers;
 }
 
 bool gemm_v3_eligible(const GemmArgs &a, int batch) {
-#ifndef CLO_GEMM_V3
-#define CLO_GEMM_V3 1
-#endif
-  static const int off = !CLO_GEMM_V3;
-  if (off || a.patch || a.ones || a.ones_b || a.col_out) return false;
+  if (a.patch || a.ones || a.ones_b || a.col_out) return false;
   if (a.A2 && (a.K1 % V3_BK != 0)) return false;
   // 32-bit byte offsets inside one k tile of one output tile
   const long lim = 1L << 29;
@@ -701,12 +692,7 @@ bool gemm_v3_eligible(const GemmArgs &a, int batch) {
 // enough rows and enough tiles.
 constexpr int V3T_BM = 256, V3T_BN = 128, V3T_WVM = 4, V3T_WVN = 2, V3T_NST = 3;
 static bool v3_use_tall(const GemmArgs &a, int batch) {
-#ifndef CLO_GEMM_V3_TALL
-#define CLO_GEMM_V3_TALL 1
-#endif
-  static const int mode = CLO_GEMM_V3_TALL;  // 0 never, 2 whenever legal
-  if (!mode || a.sym || a.M < V3T_BM || a.K < 2048) return false;   // (short k: the longer fill / drain of the tall tile loses, 4608 x 4608 x 512: 226 -> 263 us)
-  if (mode == 2) return true;
+  if (a.sym || a.M < V3T_BM || a.K < 2048) return false;   // (short k: the longer fill / drain of the tall tile loses, 4608 x 4608 x 512: 226 -> 263 us)
   const long tall_tiles = cdiv(a.M, V3T_BM) * cdiv(a.N, V3T_BN) * batch;
   // Measured (MI355X): +2-4 % on large squares (4096^3 NT 130.7 -> 135.4, 8192^3 136.4 -> 139.1 TFLOP/s); with stream-K
   // the 128 KB partial tiles cost more than the operand traffic saves (512 x 4608 x 4608: 210 -> 220 us), so the tall
@@ -719,16 +705,8 @@ static bool v3_use_tall(const GemmArgs &a, int batch) {
 // through each CU's ~30 GB/s memory pipe -- 1024^3: 15 us of MFMA work + 10 us of partial traffic --, while four times as
 // many quarter-size tiles need no (or 16 KB) partials; the register-staged 64 x 64 x 64 loop of gemm.hip that served these
 // shapes prefetches ONE k tile ahead, less than the memory latency at 0.4 us per k tile, and ran at half its MFMA rate.
-#ifndef CLO_V3S_NST
-#define CLO_V3S_NST 4
-#endif
-constexpr int V3S_BM = 64, V3S_BN = 64, V3S_WVM = 2, V3S_WVN = 2, V3S_NST = CLO_V3S_NST;
+constexpr int V3S_BM = 64, V3S_BN = 64, V3S_WVM = 2, V3S_WVN = 2, V3S_NST = 4;
 static bool v3_use_small(const GemmArgs &a, int batch) {
-#ifndef CLO_GEMM_V3_SMALL
-#define CLO_GEMM_V3_SMALL 1
-#endif
-  static const int mode = CLO_GEMM_V3_SMALL;   // 0 never
-  if (!mode) return false;
   const long tm = cdiv(a.M, V3_BM), tn = cdiv(a.N, V3_BN);
   const long tiles = (a.sym ? tm * (tm + 1) / 2 : tm * tn) * batch;
   // Measured (tools/probe_gemm_sweep_r5.py, profiles/r05_gemm_midsize_sweep.txt): a 64 x 64 tile needs 16 KB of operands per
@@ -736,11 +714,7 @@ static bool v3_use_small(const GemmArgs &a, int batch) {
   // win where few of them are in flight per unit of K: skinny outputs (min(M, N) <= 384: 128 x 2304 x 2304 29.8 -> 27.9 us,
   // 2688 x 256 x 2688 52.1 -> 46.3) and symmetric products (half the tiles: 512-row pixel Grams 46.7 -> 43.1 / 18.9 -> 17.6 us,
   // the patch products of round 4 175 -> 140 us); 512 x 2304 x 2304 loses (64 -> 81 us) and keeps the 128 x 128 tiles.
-#ifndef CLO_V3_SMALL_EPI
-#define CLO_V3_SMALL_EPI 0
-#endif
-  if (a.epi != EPI_NONE && !CLO_V3_SMALL_EPI) return false;   // (fused epilogues run the engine's generic store path per tile: C2 at 65 / 128 rows 180 -> 192 / 194 -> 201 us)
-  if (mode == 2) return tiles < 2L * kNumCU;   // (probe builds: wherever the square tiles leave the second round half empty)
+  if (a.epi != EPI_NONE) return false;   // (fused epilogues run the engine's generic store path per tile: C2 at 65 / 128 rows 180 -> 192 / 194 -> 201 us)
   // round 6: also the products the register-staged 64 x 64 x 64 loop of gemm.hip used to keep (M N <= 2^20, e. g. 1024^3: at most
   // one small tile per CU): 32.7 -> 29.5 us
   return tiles < kNumCU && (a.sym || std::min(a.M, a.N) <= 384 || (long)a.M * a.N <= 1024L * 1024L);
@@ -796,11 +770,7 @@ int launch_gemm_v3(const GemmArgs &a0, int batch, bool a_kc, bool b_kc, hipStrea
 #ifdef CLO_V3_TIMING
   s.stamps = g_v3_stamps_host;
 #endif
-#ifndef CLO_GEMM_STREAMK
-#define CLO_GEMM_STREAMK 1
-#endif
-  static const int sk_off = !CLO_GEMM_STREAMK;
-  const bool sk_ok = a.streamk && a.ws && !a.tri && !sk_off;
+  const bool sk_ok = a.streamk && a.ws && !a.tri;
   int tall = 0;
   long workers = v3_plan(a, batch, sk_ok ? a.streamk : 0, &tall);
   const int nkt = (int)cdiv(a.K, V3_BK);
@@ -840,13 +810,9 @@ int launch_gemm_v3(const GemmArgs &a0, int batch, bool a_kc, bool b_kc, hipStrea
     s.units = tiles * nkt;
     s.slots = a.ws;
     // teams of G = tiles_m members when the row tiles are few (each panel = all row tiles of one block column)
-#ifndef CLO_GEMM_SK_TEAM
-#define CLO_GEMM_SK_TEAM 1
-#endif
-    static const int team_off = !CLO_GEMM_SK_TEAM;
     s.team = 1;
     const int G = a.tiles_m;
-    if (!team_off && !a.sym && batch == 1 && (G == 2 || G == 4 || G == 8) && s.workers % (kNumXCD * G) == 0 &&
+    if (!a.sym && batch == 1 && (G == 2 || G == 4 || G == 8) && s.workers % (kNumXCD * G) == 0 &&
         (long)(s.workers / G) * 2 <= (long)a.tiles_n * nkt)
       s.team = G;
     const int rcf = v3_flags(stream, &s.flags, &s.epoch);
@@ -870,12 +836,10 @@ int launch_gemm_v3(const GemmArgs &a0, int batch, bool a_kc, bool b_kc, hipStrea
   } else {
     grid = dim3((unsigned)tiles_mat, (unsigned)(batch * a.splitk));
   }
-#define CLO_V3(AK, BK_, SKV, BMV, BNV, WM_, WN_, NSTV) CLO_V3K(AK, BK_, SKV, BMV, BNV, WM_, WN_, NSTV, 1)
-#define CLO_V3K(AK, BK_, SKV, BMV, BNV, WM_, WN_, NSTV, KGV)                                                   \
+#define CLO_V3(AK, BK_, SKV, BMV, BNV, WM_, WN_, NSTV)                                                         \
   {                                                                                                            \
-    auto kern = gemm_v3_kernel<AK, BK_, BMV, BNV, WM_, WN_, NSTV, SKV, KGV>;                                   \
-    const size_t smem = (size_t)KGV * NSTV * (BMV + BNV) * V3_BK * sizeof(float) +                             \
-                        (KGV > 1 ? (size_t)BMV * BNV * sizeof(float) : 0);   /* + the k groups' hand-over area */ \
+    auto kern = gemm_v3_kernel<AK, BK_, BMV, BNV, WM_, WN_, NSTV, SKV>;                                        \
+    const size_t smem = (size_t)NSTV * (BMV + BNV) * V3_BK * sizeof(float);                                    \
     static bool attr_done[64] = {};  /* per device: the attribute belongs to the device's copy of the kernel */ \
     bool &attr_set = attr_done[dev_ & 63];                                                                     \
     if (!attr_set) {                                                                                           \
@@ -885,7 +849,7 @@ int launch_gemm_v3(const GemmArgs &a0, int batch, bool a_kc, bool b_kc, hipStrea
       if (rc_ != CLO_OK) return rc_;                                                                           \
       attr_set = true;                                                                                         \
     }                                                                                                          \
-    hipLaunchKernelGGL(kern, grid, dim3(WM_ * WN_ * 64 * KGV), smem, stream, a, s);                            \
+    hipLaunchKernelGGL(kern, grid, dim3(WM_ * WN_ * 64), smem, stream, a, s);                                  \
   }
 #define CLO_V3L(SKV, BMV, BNV, WM_, WN_, NSTV)                            \
   if (a_kc && b_kc) CLO_V3(true, true, SKV, BMV, BNV, WM_, WN_, NSTV)     \
@@ -896,29 +860,15 @@ int launch_gemm_v3(const GemmArgs &a0, int batch, bool a_kc, bool b_kc, hipStrea
     if (sk) { CLO_V3L(true, V3T_BM, V3T_BN, V3T_WVM, V3T_WVN, V3T_NST) }
     else { CLO_V3L(false, V3T_BM, V3T_BN, V3T_WVM, V3T_WVN, V3T_NST) }
   } else if (tall == 2) {
-    // Eight waves per small tile (two k groups, KG = 2 above) once the k loop is long enough to split: BUILT AND MEASURED in
-    // round 6, NOT the default -- it loses 10 - 25 % on every shape it applies to (profiles/r06_gemm_kgroup_ab.txt:
-    // 128 x 2304 x 2304 34.9 vs 28.6 us, 384 x 1152 x 1152 32.9 vs 26.2, 256 x 2304 x 2304 49.6 vs 44.1).  The four-wave
-    // tile needs 64 KB of LDS, so TWO of them share a CU already: eight waves per CU from two independent workgroups, whose
-    // barriers do not couple, beat eight waves of one workgroup (144 KB: one per CU) that all meet at every k tile.
-#ifndef CLO_GEMM_V3_KG
-#define CLO_GEMM_V3_KG 1
-#endif
-    const long kspan = a.splitk > 1 ? a.k_per_split : a.K;
+    // (eight waves per small tile, two k groups, lost 10 - 25 % on every shape it applied to: profiles/r06_gemm_kgroup_ab.txt,
+    // DESIGN.md section 3.2)
     if (sk) { CLO_V3L(true, V3S_BM, V3S_BN, V3S_WVM, V3S_WVN, V3S_NST) }
-    else if (CLO_GEMM_V3_KG == 2 && kspan >= 8 * V3_BK) {
-      if (a_kc && b_kc) CLO_V3K(true, true, false, V3S_BM, V3S_BN, V3S_WVM, V3S_WVN, V3S_NST, 2)
-      else if (a_kc) CLO_V3K(true, false, false, V3S_BM, V3S_BN, V3S_WVM, V3S_WVN, V3S_NST, 2)
-      else if (b_kc) CLO_V3K(false, true, false, V3S_BM, V3S_BN, V3S_WVM, V3S_WVN, V3S_NST, 2)
-      else CLO_V3K(false, false, false, V3S_BM, V3S_BN, V3S_WVM, V3S_WVN, V3S_NST, 2)
-    }
     else { CLO_V3L(false, V3S_BM, V3S_BN, V3S_WVM, V3S_WVN, V3S_NST) }
   } else {
     if (sk) { CLO_V3L(true, V3_BM, V3_BN, V3_WVM, V3_WVN, V3_NST) }
     else { CLO_V3L(false, V3_BM, V3_BN, V3_WVM, V3_WVN, V3_NST) }
   }
 #undef CLO_V3L
-#undef CLO_V3K
 #undef CLO_V3
   CLO_CHECK_LAUNCH("gemm_v3_kernel");
   return CLO_OK;

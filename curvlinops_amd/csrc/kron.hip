@@ -76,11 +76,7 @@ inline long kron_pad_floats(int K, int C1, int R1, int C2, int R2) {   // S2p, X
 int kron_apply(float *Y, const Fac &E1, const Fac &E2, const float *X, int K, float *T, float *gws, long gws_floats,
                hipStream_t st) {
   const int C1 = E1.cols, C2 = E2.cols, R1 = E1.rows, R2 = E2.rows;
-#ifndef CLO_KRON_PAD
-#define CLO_KRON_PAD 1
-#endif
-  static const int pad_on = CLO_KRON_PAD;
-  if (pad_on && kron_wants_pad(K, C1, C2, R2) && gws_floats >= kron_pad_floats(K, C1, R1, C2, R2) + (1L << 20)) {
+  if (kron_wants_pad(K, C1, C2, R2) && gws_floats >= kron_pad_floats(K, C1, R1, C2, R2) + (1L << 20)) {
     const long C2p = pad4k(C2), R2p = pad4k(R2);
     float *S2p = gws, *Xp = S2p + R2p * C2p, *Tp = Xp + (long)K * C1 * C2p, *Yp = Tp + (long)K * C1 * R2p;
     float *g2 = Yp + (long)K * R1 * R2p;

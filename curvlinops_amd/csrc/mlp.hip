@@ -21,7 +21,6 @@
 #include "clo_common.h"
 #include "gemm.h"
 #include "mlp_loss.h"
-#include "persist_gate.h"
 
 #include <mutex>
 
@@ -42,28 +41,12 @@ __device__ __forceinline__ float fma4(const float4 &a, const float4 &b, float ac
 }
 __device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-// streamed-once data: non-temporal policy (global_load_dwordx4 ... nt)
-__device__ __forceinline__ float4 ld4nt(const float *p) {
-  typedef float __attribute__((ext_vector_type(4))) v4;
-  const v4 v = __builtin_nontemporal_load(reinterpret_cast<const v4 *>(p));
-  return make_float4(v.x, v.y, v.z, v.w);
-}
 __device__ __forceinline__ void st4(float *p, const float4 &v) { *reinterpret_cast<float4 *>(p) = v; }
+// the result stream is written once and not read again by the matvec: nt stores (+1 % measured)
 __device__ __forceinline__ void st4nt(float *p, const float4 &v) {
   typedef float __attribute__((ext_vector_type(4))) v4;
   __builtin_nontemporal_store(v4{v.x, v.y, v.z, v.w}, reinterpret_cast<v4 *>(p));
 }
-#ifdef CLO_NT_WEIGHTS
-#define CLO_LDW ld4nt
-#else
-#define CLO_LDW ld4
-#endif
-// the result stream is written once and not read again by the matvec: nt stores (+1 % measured)
-#ifdef CLO_TEMPORAL_STORES
-#define CLO_STW st4
-#else
-#define CLO_STW st4nt
-#endif
 
 // Load the lane's 4 floats of 256-wide sub-slice q of a row (k offset k0).
 // VEC: lane owns 4 consecutive floats (one 16-byte load); scalar: 4 loads strided by 64.
@@ -385,7 +368,7 @@ __global__ __launch_bounds__(MF_WAVES * 64) void fwd_mfma_kernel(
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
-      for (int g = 0; g < RG; ++g) gr.av[u][g] = CLO_LDW(pA[g] + (st0 + u) * 16);
+      for (int g = 0; g < RG; ++g) gr.av[u][g] = ld4(pA[g] + (st0 + u) * 16);
   };
   auto mma = [&](const Group &gr, int st0) {
 #pragma unroll
@@ -508,7 +491,7 @@ __global__ __launch_bounds__(WAVES * 64) void fwd_mfma_first_kernel(
 #pragma unroll
     for (int u = 0; u < U; ++u) {
 #pragma unroll
-      for (int g = 0; g < RG; ++g) av[u][g] = CLO_LDW(pA[g] + (step + u) * 16);
+      for (int g = 0; g < RG; ++g) av[u][g] = ld4(pA[g] + (step + u) * 16);
       bv[u] = ld4(pB + (step + u) * 16);
     }
     __builtin_amdgcn_sched_barrier(0);  // every load of the group is issued before the first MFMA waits
@@ -860,7 +843,7 @@ __device__ __forceinline__ void bwd_block(
           }
           float *po = out_W + (long)jt * d_in;
           if (VEC) {
-            if (col_ok) CLO_STW(po + i0 + lane * 4, r);
+            if (col_ok) st4nt(po + i0 + lane * 4, r);
           } else {
             const float *pr = reinterpret_cast<const float *>(&r);
 #pragma unroll
@@ -930,10 +913,7 @@ __global__ __launch_bounds__(512, 4) void bwd_fused_kernel(
 constexpr int OUTER_MAXL = 16;
 // rows per block: 32 (4 per wave) measured best on C2 (whole matvec: 128 rows 55.0 us, 64: 53.2, 32: 52.5,
 // 256: 60.3) -- short blocks hide each other's staging prologue
-#ifndef CLO_OUTER_ROWS
-#define CLO_OUTER_ROWS 32
-#endif
-constexpr int OUTER_ROWS = CLO_OUTER_ROWS;
+constexpr int OUTER_ROWS = 32;
 struct OuterAllArgs {
   int nlayers;
   int first_block[OUTER_MAXL + 1];
@@ -1232,9 +1212,6 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const HeadBwdArgs p) {
 // 64 banks, so those writes are conflict-free too; the fragment reads pay one extra cycle on three banks)
 constexpr int mid_ldd(int NT) { return NT <= 2 ? 49 : 81; }
 
-#ifndef CLO_MIDF_SU
-#define CLO_MIDF_SU 16
-#endif
 template <int NT, bool HAS_DA, int WV>
 __global__ __launch_bounds__(WV * 64) void mid_fwd_kernel(
     const float *__restrict__ W, const float *__restrict__ VW, const float *__restrict__ a_in,
@@ -1273,8 +1250,8 @@ __global__ __launch_bounds__(WV * 64) void mid_fwd_kernel(
   auto load = [&](Group &gr, int st0) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      gr.w[u] = CLO_LDW(pW + (st0 + u) * 16);
-      gr.v[u] = CLO_LDW(pV + (st0 + u) * 16);
+      gr.w[u] = ld4(pW + (st0 + u) * 16);
+      gr.v[u] = ld4(pV + (st0 + u) * 16);
     }
   };
   const int nfull = klen >> 4, ngroups = nfull / U;
@@ -1288,10 +1265,10 @@ __global__ __launch_bounds__(WV * 64) void mid_fwd_kernel(
     w_first = false;
   }
 
-  {  // stage B: columns [0, NP) = rows of a, [NP, 2 NP) = rows of da; zero beyond N rows / klen.  CLO_MIDF_SU loads in flight per thread
+  {  // stage B: columns [0, NP) = rows of a, [NP, 2 NP) = rows of da; zero beyond N rows / klen.  SU loads in flight per thread
     // (round 6: one load, one LDS write per trip was 16 dependent round trips at 64 rows -- 7.1 us before the first MFMA,
     // tools/r6/probe_mid_fwd_timeline.py); unconditional loads at clamped addresses, zeroed afterwards
-    constexpr int NC = (HAS_DA ? 2 : 1) * NP, SU = NT >= 3 ? CLO_MIDF_SU : 8;   // (16 in flight lose 1.5 - 2 us up to 32 rows, win 1.2 us at 64)
+    constexpr int NC = (HAS_DA ? 2 : 1) * NP, SU = NT >= 3 ? 16 : 8;   // (16 in flight lose 1.5 - 2 us up to 32 rows, win 1.2 us at 64)
     const int q4 = (k_per_block + 3) >> 2, total = NC * q4;
     for (int e0 = tid; e0 < total; e0 += SU * WV * 64) {
       float4 v[SU];
@@ -1456,7 +1433,7 @@ __global__ __launch_bounds__(512) void mid_full_kernel(
 #pragma unroll
     for (int u = 0; u < U; ++u) {
 #pragma unroll
-      for (int g = 0; g < RG; ++g) av[u][g] = CLO_LDW(pA[g] + (step + u) * 16);
+      for (int g = 0; g < RG; ++g) av[u][g] = ld4(pA[g] + (step + u) * 16);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         bv[u][t] = ld4(a_in + offB[t] + (step + u) * 16);
@@ -1863,7 +1840,7 @@ __device__ __forceinline__ void mid_outer_body(const MidOuterArgs &p, int block,
           const float4 od = ld4(po);
           v.x += p.beta * od.x; v.y += p.beta * od.y; v.z += p.beta * od.z; v.w += p.beta * od.w;
         }
-        CLO_STW(po, v);
+        st4nt(po, v);
       }
     }
 #ifdef CLO_MID_TIMING
@@ -1885,9 +1862,6 @@ __global__ __launch_bounds__(512) void mid_outer_kernel(const MidOuterArgs p) {
 // through a double-buffered LDS tile 64 columns at a time (global loads of chunk c + 1 in flight behind the MFMAs and stores of chunk c,
 // one barrier per chunk), and the result leaves as 4 rows x 256 bytes per store instruction.  Ranges are sized so that the whole grid
 // is resident at once (about two blocks per CU).
-#ifndef CLO_MO2_STAGE_DELTA
-#define CLO_MO2_STAGE_DELTA 1
-#endif
 constexpr int MO2_ROWS = 128, MO2_CW = 64, MO2_DPITCH = 144;
 struct MidOuter2Args {
   int nlayers;
@@ -1953,7 +1927,7 @@ __global__ __launch_bounds__(512) void mid_outer2_kernel(const MidOuter2Args p) 
   float af[KS];
   const MidDelta &mdl = p.md[l];
   const long ldd = mdl.ld_delta ? mdl.ld_delta : d_out;
-  if (CLO_MO2_STAGE_DELTA && !mdl.dslabs && ((ldd | (long)d_out) & 3) == 0 && (((unsigned long)mdl.delta) & 15ul) == 0) {
+  if (!mdl.dslabs && ((ldd | (long)d_out) & 3) == 0 && (((unsigned long)mdl.delta) & 15ul) == 0) {
     // a plain, aligned delta array: the block's strip [NP][128 rows j] goes through LDS -- coalesced 16-byte loads, 512 bytes per batch
     // row -- instead of KS four-byte loads per lane that each touch four rows x 64 bytes (the buffer of the a_{l-1} chunks is free until
     // the first chunk is stored; pitch 144: the four k groups of a fragment read hit disjoint banks)
@@ -2025,7 +1999,7 @@ __global__ __launch_bounds__(512) void mid_outer2_kernel(const MidOuter2Args p) 
             const float4 od = ld4(po);
             v.x += p.beta * od.x; v.y += p.beta * od.y; v.z += p.beta * od.z; v.w += p.beta * od.w;
           }
-          CLO_STW(po, v);
+          st4nt(po, v);
         }
       }
     }
@@ -2042,9 +2016,6 @@ __global__ __launch_bounds__(512) void mid_outer2_kernel(const MidOuter2Args p) 
 template <typename K>
 static int set_smem(K kernel, size_t bytes);
 // the outer products of `count` layers (fields of a MidOuterArgs filled as for mid_outer_kernel) in one mid_outer2_kernel launch
-#ifndef CLO_MO2_PER_CU
-#define CLO_MO2_PER_CU 2
-#endif
 template <int NT>
 static int launch_mid_outer2(const MidOuterArgs &oa, int count, float beta, int N, hipStream_t st) {
   constexpr int NP = 16 * NT;
@@ -2055,10 +2026,11 @@ static int launch_mid_outer2(const MidOuterArgs &oa, int count, float beta, int 
   o2.nlayers = count; o2.alpha = oa.alpha; o2.beta = beta; o2.N = N;
   long strip_cols = 0;
   for (int k = 0; k < count; ++k) strip_cols += cdiv(oa.d_out[k], MO2_ROWS) * (long)oa.d_in[k];
-  // about CLO_MO2_PER_CU resident blocks per CU (2, 3, 4 and 6 measured alike; 1 is 7 % slower), ranges of whole 64-column chunks
+  // about MO2_PER_CU resident blocks per CU (2, 3, 4 and 6 measured alike; 1 is 7 % slower), ranges of whole 64-column chunks
   // (ranges of a multiple of 16 columns that fill the two-per-CU grid more evenly were measured: no difference, 65 ... 128 rows)
+  constexpr long MO2_PER_CU = 2;
   const size_t smem_blk = (size_t)std::max(2 * NP * MO2_CW, NP * MO2_DPITCH) * sizeof(float);
-  const long per_cu = std::max<long>(1, std::min<long>(CLO_MO2_PER_CU, (160 * 1024) / (long)smem_blk));   // (beyond 128 rows: one block per CU)
+  const long per_cu = std::max<long>(1, std::min<long>(MO2_PER_CU, (160 * 1024) / (long)smem_blk));   // (beyond 128 rows: one block per CU)
   const int cr = (int)std::max<long>(MO2_CW, cdiv(cdiv(strip_cols, per_cu * kNumCU), MO2_CW) * MO2_CW);
   int nb2 = 0;
   for (int k = 0; k < count; ++k) {
@@ -2078,19 +2050,6 @@ static int launch_mid_outer2(const MidOuterArgs &oa, int count, float beta, int 
   else hipLaunchKernelGGL((mid_outer2_kernel<NT, false>), dim3(nb2), dim3(512), smem2, st, o2);
   CLO_CHECK_LAUNCH("mid_outer2_kernel");
   return CLO_OK;
-}
-
-// Round 6: the data chain's step delta_{l-1} = delta_l W_l and the outer products that only need delta_l (layer l, and the
-// head's layer at the first step) in ONE launch: the read-only sweep of W_l and the write-only stream of out_W_l are
-// independent, and as two launches each paid its own boundary, staging prologue and drain with one workgroup per CU
-// (C2, 16 rows: 11.6 + 12.3 us).  The data-chain blocks come first (the next step waits for them).
-template <int NT, bool ACCUM, int CW>
-__global__ __launch_bounds__(512) void mid_bwd_merged_kernel(const MidDprevArgs q, const MidOuterArgs p, int n_dprev,
-                                                             int dprev_gx) {
-  extern __shared__ __attribute__((aligned(16))) float smem_m[];
-  const int b = blockIdx.x;
-  if (b < n_dprev) mid_dprev_body<NT>(q, b % dprev_gx, b / dprev_gx, smem_m);
-  else mid_outer_body<NT, ACCUM, CW>(p, b - n_dprev, smem_m);
 }
 
 // delta_l [N][d] = (sum of the row-range slabs of mid_dprev_kernel) x act'(z_l): beyond 32 batch rows the
@@ -2451,25 +2410,16 @@ __global__ void small_outer_reduce_kernel(float *__restrict__ out, const float *
 //   dprev    : GEMM delta_{l-1} = phi' * (W_l^T delta_l) with N K columns
 // Tangents / deltas are stored feature-major: [d_l][N][K].  N <= 8 rows per pass, K % 4 == 0, K <= 64.
 // ------------------------------------------------------------------------------------------
-#ifndef CLO_KC_WAVES
-#define CLO_KC_WAVES 8
-#endif
-constexpr int KC_WAVES = CLO_KC_WAVES;   // waves of a kfwd block: split the contraction among themselves
+constexpr int KC_WAVES = 8;   // waves of a kfwd block: split the contraction among themselves
                               // (1 tile x 8 waves measured best among {1,2,3,4} tiles x {1,2,4,8} waves)
-#ifndef CLO_KC_TPW
-#define CLO_KC_TPW 1
-#endif
-constexpr int KC_TPW = CLO_KC_TPW;     // MFMA tiles per wave (1 measured best: more, smaller blocks)
+constexpr int KC_TPW = 1;     // MFMA tiles per wave (1 measured best: more, smaller blocks)
 
 // One MFMA tile = 16 "columns" c = (feature f = c / G, column quad kq = c % G), G = K / 4; lane
 // (c, s = lane >> 4) loads ONE float4 V[j + f][i][4 kq ..] per i and feeds four MFMAs (one per
 // column of the quad), all with the A operand a[n][i].  k-slot s takes i = ib + 4 s + t in step t,
 // so the A operand is one float4 of row n per 16 i.
-#ifndef CLO_KC_WPE
-#define CLO_KC_WPE 1
-#endif
 template <bool ACC, int TPW, int KW>
-__global__ __launch_bounds__(KW * 64, CLO_KC_WPE) void kfwd_stream_kernel(
+__global__ __launch_bounds__(KW * 64, 1) void kfwd_stream_kernel(
     const float *__restrict__ V, long ldk, const float *__restrict__ Vb,
     const float *__restrict__ a, const float *__restrict__ dphi, float *__restrict__ dA, int N,
     int K, int d_in, int d_out) {
@@ -2605,23 +2555,21 @@ __global__ __launch_bounds__(KW * 64, CLO_KC_WPE) void kfwd_stream_kernel(
     cg = wrap ? 0 : cg + 1;
     ct = wrap ? ct + 1 : ct;
   };
-#ifndef CLO_KF_DEPTH
-#define CLO_KF_DEPTH 2
-#endif
-  // register ring of CLO_KF_DEPTH groups: DEPTH - 1 groups of loads are in flight while one feeds the MFMAs.  The
+  // register ring of DEPTH groups: DEPTH - 1 groups of loads are in flight while one feeds the MFMAs.  The
   // sched_barriers pin "issue the loads, THEN the MFMAs": the machine scheduler otherwise sinks the loads into the
   // MFMA sequence to save registers, which shortens the prefetch distance to half a step.
-  Group ring[CLO_KF_DEPTH];
+  constexpr int DEPTH = 2;
+  Group ring[DEPTH];
   zero_acc();
 #pragma unroll
-  for (int q = 0; q < CLO_KF_DEPTH - 1; ++q) {
+  for (int q = 0; q < DEPTH - 1; ++q) {
     load(ring[q], lt, lg);
     next_load();
   }
-  for (int s0 = 0; s0 < nsteps; s0 += CLO_KF_DEPTH) {
+  for (int s0 = 0; s0 < nsteps; s0 += DEPTH) {
 #pragma unroll
-    for (int q = 0; q < CLO_KF_DEPTH; ++q) {
-      load(ring[(q + CLO_KF_DEPTH - 1) % CLO_KF_DEPTH], lt, lg);
+    for (int q = 0; q < DEPTH; ++q) {
+      load(ring[(q + DEPTH - 1) % DEPTH], lt, lg);
       next_load();
       __builtin_amdgcn_sched_barrier(0);
       step(ring[q], s0 + q);
@@ -2654,6 +2602,7 @@ __global__ void pack_at_multi_kernel(const PackMulti p, float *__restrict__ aT) 
 // out[j][i][k] = beta out[j][i][k] + sum_n aT[i][n] delta[j][n][k] ; out_b[j][k] likewise with 1.
 // One block per output feature j; lane = (input feature, column quad): a wave instruction stores
 // (64 / G) consecutive rows of K floats = one contiguous run of the result.
+constexpr int KO_U = 4;   // wave instructions per trip of kouter_stream_kernel
 template <bool ACCUM>
 __global__ __launch_bounds__(256) void kouter_stream_kernel(
     float *__restrict__ out, long ldk, float *__restrict__ out_b, const float *__restrict__ aT,
@@ -2682,10 +2631,7 @@ __global__ __launch_bounds__(256) void kouter_stream_kernel(
     *reinterpret_cast<float4 *>(ob) = sb;
   }
   float *oj = out + (long)j * d_in * ldk + 4 * kq;
-#ifndef CLO_KO_U
-#define CLO_KO_U 4
-#endif
-  constexpr int U = CLO_KO_U;
+  constexpr int U = KO_U;
   const int step = 4 * IPW;  // input features per block trip
   for (int i0 = ibeg + wave * IPW + io; i0 < iend; i0 += U * step) {
     float4 x0[U], x1[U], old[U];
@@ -2708,7 +2654,7 @@ __global__ __launch_bounds__(256) void kouter_stream_kernel(
         o.x = fmaf(xs[n], d[n].x, o.x); o.y = fmaf(xs[n], d[n].y, o.y);
         o.z = fmaf(xs[n], d[n].z, o.z); o.w = fmaf(xs[n], d[n].w, o.w);
       }
-      CLO_STW(oj + (long)i * ldk, o);
+      st4nt(oj + (long)i * ldk, o);
     }
   }
 }
@@ -3046,10 +2992,8 @@ constexpr int MF_RG = 2;
 constexpr int MF1_WAVES = 8, MF1_RG = 2, MF1_U = 4;  // fwd_mfma_first_kernel
 static int mfma_kpb(int d_in, int d_out) {
   const long row_blocks = cdiv(d_out, MF_WAVES * MF_RG * 8);
-#ifndef CLO_MF_BPC
-#define CLO_MF_BPC 2
-#endif
-  long ksplit = std::max<long>(1, cdiv(CLO_MF_BPC * kNumCU, row_blocks));
+  constexpr long blocks_per_cu = 2;
+  long ksplit = std::max<long>(1, cdiv(blocks_per_cu * kNumCU, row_blocks));
   ksplit = std::min<long>(ksplit, std::max<long>(1, d_in / 64));
   ksplit = std::min<long>(ksplit, 16);  // slab merges stay short (narrow layers are tiny anyway)
   long kpb = cdiv(cdiv(d_in, ksplit), 32) * 32;
@@ -3061,10 +3005,7 @@ static int bwd_jb(int d_in, int d_out, bool dprev) {
   const long cchunks = cdiv(d_in, CW);
   long jb = cdiv(kNumCU, cchunks);                    // ~1 block per CU
   jb = std::min<long>(jb, cdiv(d_out, 64));           // >= 64 rows (8 per wave) per block
-#ifndef CLO_DPREV_JB
-#define CLO_DPREV_JB 24
-#endif
-  if (dprev) jb = std::min<long>(jb, CLO_DPREV_JB);   // bound the slab traffic (32 -> 24: -1 us on C2)
+  if (dprev) jb = std::min<long>(jb, 24);   // bound the slab traffic (32 -> 24: -1 us on C2)
   jb = std::max<long>(jb, cdiv(d_out, 1024));         // <= 1024 rows of delta in LDS
   return (int)std::max<long>(1, jb);
 }
@@ -3383,439 +3324,12 @@ extern "C" int clo_mlp_bwd_layer(const float *W, const float *delta, const float
 // Scratch comes out of the GEMM slab area `gws` (unused on this path): forward slabs | head partials |
 // two regions of delta slabs (ping-pong over the layers).
 // ------------------------------------------------------------------------------------------
-// ------------------------------------------------------------------------------------------
-// Round 6: layers 1 and 2 of the forward + JVP pass of the 9 ... 64-row chain in ONE persistent launch
-// (three-layer nets with a narrow head -- BASELINE config C2's class; reference ggn.py:61-66, the jvp half).
-// As separate launches (mid_full_kernel, mid_fwd_kernel) the two weight streams of 22 + 58 MB each paid a
-// launch boundary, a staging prologue and a drain with one workgroup per CU (C2, 16 / 32 / 64 rows:
-// 10 + 15 / 15 + 23 / 21 + 40 us).  Here 256 workgroups form the 16 x 16 grid of csrc/mlp_mega.hip over layer 2:
-// workgroup (fb, kb) first computes its <= 16 layer-1 features of K range kb for all rows (in-block split-K over the
-// eight waves, as mid_full_kernel), publishes them write-through, and meets the 15 other workgroups of its COLUMN
-// group on one counter -- the only seam; the W2 / V2 fragments of its tile are requested before it polls.  Then
-// the [a1 ; da1] operand of the K range is staged in LDS and the tile's partial z2 / dz2 (three products per step)
-// go to the slab of split kb: exactly what mid_fwd_kernel with 16 K ranges would write, so head_fwd_kernel finishes
-// the layer as before.  Counters are monotonic (target = 16 x launch number, the launch number from a 64-bit count of
-// finished workgroups), every spin is bounded; a timeout marks the slab with NaN and raises the device's fault word.
-// ------------------------------------------------------------------------------------------
-namespace clo {
-constexpr int MFU_G = 256, MFU_T = 512, MFU_MAXS = 11, MFU_KR = 16 * MFU_MAXS, MFU_MAXCH = 11;
-constexpr int MFU_SYNC_WORDS = 32 * 20 + 4096;   // (+ timing slots of -DCLO_MFU_TIMING builds)   // line 0: finished-workgroup count (64 bit); line 1: abort word; lines 2 .. 17: column groups
-
-struct MidFusedArgs {
-  const float *W1, *b1, *V1, *Vb1, *X, *W2, *V2;
-  float *a1, *da1, *dphi1;   // [N][d1]
-  float *part;               // [16][2][NP][d2]
-  int N, d0, d1, d2, act1;
-  unsigned *sync;
-  unsigned *fault;
-  unsigned spin_limit;
-};
-
-__device__ __forceinline__ f32x4 mfu_ld_sc1(__amdgpu_buffer_rsrc_t rs, long off_floats) {
-  typedef unsigned int u32x4m __attribute__((ext_vector_type(4)));
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)(off_floats * 4), 0, 16));
-}
-__device__ __forceinline__ void mfu_st_sc1(__amdgpu_buffer_rsrc_t rs, long off_floats, f32x4 v) {
-  typedef unsigned int u32x4m __attribute__((ext_vector_type(4)));
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4m, v), rs, (unsigned)(off_floats * 4), 0, 16);
-}
-
-#ifdef CLO_MFU_TIMING
-#define MFU_STAMP(i) do { if ((tid & 63) == 0 && (blockIdx.x & 63) == 0) reinterpret_cast<unsigned long long *>(p.sync + 32 * 20)[((blockIdx.x >> 6) * 8 + (tid >> 6)) * 16 + (i)] = wall_clock64(); } while (0)
-#else
-#define MFU_STAMP(i) do { } while (0)
-#endif
-template <int NT>
-__global__ __launch_bounds__(MFU_T) void mid_fused_fwd_kernel(const MidFusedArgs p) {
-  constexpr int NP = 16 * NT, WAVES = 8, RG = 2, XW = WAVES - 1;   // wave XW: the exchange wave (owns no early tile loads)
-  constexpr int LDB = MFU_KR + 4;
-  constexpr int PRE = 4;                                            // tile steps requested before the seam
-  constexpr int SPC = (NP * (MFU_KR / 4) + MFU_T - 1) / MFU_T;      // 16-byte pieces per thread and staged array
-  extern __shared__ __attribute__((aligned(16))) float s_fu[];   // phase 1: [WAVES][RG][NT][2][4][32]; phase 2: [2 NP][LDB]
-  __shared__ unsigned s_flag;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int idx = lane & 15, s4 = (lane >> 4) * 4;
-  const int w = blockIdx.x;
-  const int N = p.N, d0 = p.d0, d1 = p.d1, d2 = p.d2;
-  // ---- geometry: workgroup w runs on XCD w % 8 (observed; used for speed only): a column group shares one L2
-  const int fb = w >> 4, kb = 2 * (w & 7) + ((w >> 3) & 1);
-  const int S1 = d1 >> 4;
-  const int ks0 = kb * S1 / 16, ns = (kb + 1) * S1 / 16 - ks0;            // k16 steps of the K range (<= MFU_MAXS)
-  const int k0 = ks0 * 16, kr = ns * 16;
-  const int kq = kr >> 2;
-  const int q0 = fb * kq / 16, nf1 = 4 * ((fb + 1) * kq / 16 - q0);       // layer-1 slice of this workgroup (<= 16 features)
-  const int jA = k0 + 4 * q0;
-  const int C2 = (d2 + 15) >> 4;                                           // 16-feature chunks of layer 2
-  const int c0 = fb * C2 / 16, nch = (fb + 1) * C2 / 16 - c0;              // chunks of block fb (<= MFU_MAXCH)
-  // ---- launch number from the count of finished workgroups (a late starter reads the same quotient)
-  unsigned *sy = p.sync;
-  const unsigned long long done = __hip_atomic_load(reinterpret_cast<unsigned long long *>(sy), __ATOMIC_RELAXED,
-                                                    __HIP_MEMORY_SCOPE_AGENT);
-  const unsigned target = (unsigned)(16ull * (done / MFU_G + 1ull));
-  unsigned *c_err = sy + 32, *c_col = sy + 32 * (2 + kb);
-  MFU_STAMP(0);
-
-  float4 tw[MFU_MAXS], tv[MFU_MAXS];   // fragments of one 16-feature chunk of the layer-2 tile: [W row | V row] per k16 step
-  auto rows_of = [&](int ch, const float *&pW, const float *&pV) {
-    const int row = min((c0 + ch) * 16 + idx, d2 - 1);
-    pW = p.W2 + (long)row * d1 + k0 + s4;
-    pV = p.V2 + (long)row * d1 + k0 + s4;
-  };
-  const float *pW0, *pV0;
-  rows_of(min(wave, max(nch - 1, 0)), pW0, pV0);   // the wave's first chunk (chunks wave, wave + 8)
-  __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(p.a1, 0, (int)((long)N * d1 * 4), 0x00020000);
-  __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(p.da1, 0, (int)((long)N * d1 * 4), 0x00020000);
-
-  // =====================================================================================
-  // phase 1: layer 1 for features [jA, jA + nf1), all rows: the eight waves split K (as mid_full_kernel)
-  // =====================================================================================
-  {
-    const int kpw = (int)(((d0 + 7) / 8 + 15) / 16) * 16;
-    const int kb0 = min(wave * kpw, d0);
-    const int klen = min(d0, kb0 + kpw) - kb0;   // multiple of 4 (d0 % 16 == 0), may be 0
-    const int jlast = max(jA + nf1 - 1, jA);
-    const float *pA[RG];
-#pragma unroll
-    for (int g = 0; g < RG; ++g) {
-      const int row = min(jA + g * 8 + (idx & 7), jlast);
-      pA[g] = ((idx >= 8) ? p.V1 : p.W1) + (long)row * d0 + kb0 + s4;
-    }
-    long offB[NT];
-    unsigned bmask[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int n = t * 16 + idx;
-      bmask[t] = n < N ? 0xffffffffu : 0u;
-      offB[t] = (long)min(n, N - 1) * d0 + kb0 + s4;
-    }
-    f32x4 acc1[RG][NT];
-#pragma unroll
-    for (int g = 0; g < RG; ++g)
-#pragma unroll
-      for (int t = 0; t < NT; ++t) acc1[g][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto masked = [](float4 v, unsigned m) {
-      return make_float4(__uint_as_float(__float_as_uint(v.x) & m), __uint_as_float(__float_as_uint(v.y) & m),
-                         __uint_as_float(__float_as_uint(v.z) & m), __uint_as_float(__float_as_uint(v.w) & m));
-    };
-    constexpr int U = NT <= 2 ? 4 : 2;
-    const int nfull = klen >> 4;
-    int step = 0;
-    for (; step + U <= nfull; step += U) {
-      float4 av[U][RG], bv[U][NT];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-#pragma unroll
-        for (int g = 0; g < RG; ++g) av[u][g] = CLO_LDW(pA[g] + (step + u) * 16);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) bv[u][t] = ld4(p.X + offB[t] + (step + u) * 16);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          const float4 x = masked(bv[u][t], bmask[t]);
-#pragma unroll
-          for (int g = 0; g < RG; ++g) {
-            acc1[g][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u][g].x, x.x, acc1[g][t], 0, 0, 0);
-            acc1[g][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u][g].y, x.y, acc1[g][t], 0, 0, 0);
-            acc1[g][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u][g].z, x.z, acc1[g][t], 0, 0, 0);
-            acc1[g][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u][g].w, x.w, acc1[g][t], 0, 0, 0);
-          }
-        }
-    }
-    for (; step * 16 < klen; ++step) {   // leftover full steps and the partial one
-      const bool ok = step * 16 + s4 < klen;
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const float4 x = masked(ld4(p.X + offB[t] + (ok ? step * 16 : 0)), ok ? bmask[t] : 0u);
-#pragma unroll
-        for (int g = 0; g < RG; ++g) {
-          const float4 a = ld4(pA[g] + (ok ? step * 16 : 0));
-          acc1[g][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, x.x, acc1[g][t], 0, 0, 0);
-          acc1[g][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, x.y, acc1[g][t], 0, 0, 0);
-          acc1[g][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, x.z, acc1[g][t], 0, 0, 0);
-          acc1[g][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, x.w, acc1[g][t], 0, 0, 0);
-        }
-      }
-    }
-    MFU_STAMP(1);
-    // The first PRE steps of the wave's first tile chunk, behind the layer-1 loads.  A CU's vector-memory pipe delivers in
-    // issue order: whatever is requested here is in the way of the seam's traffic below, so it is only as much as the seam
-    // takes to run, and the exchange wave requests nothing.
-    if (wave != XW) {
-#pragma unroll
-      for (int st = 0; st < PRE; ++st) {
-        tw[st] = CLO_LDW(pW0 + min(st, ns - 1) * 16);
-        tv[st] = CLO_LDW(pV0 + min(st, ns - 1) * 16);
-      }
-    }
-    // per wave: z = D rows 0..7 (W1 x), dz = D rows 8..15 (V1 x), brought to the lanes q < 2; merge the waves through LDS
-    const int q = lane >> 4, col = lane & 15;
-#pragma unroll
-    for (int g = 0; g < RG; ++g)
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float v = acc1[g][t][r];
-          const float up = __shfl(v, (lane + 32) & 63, 64);
-          if (q < 2) {
-            float *dst = s_fu + ((((wave * RG + g) * NT + t) * 2) * 4 + r) * 32 + lane;
-            dst[0] = v;
-            dst[4 * 32] = up;
-          }
-        }
-    __syncthreads();
-    MFU_STAMP(2);
-    if (wave == XW) {
-      // ---- the exchange wave: finish the slice (bias, activation), publish it write-through, arrive, poll
-      __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(p.dphi1, 0, (int)((long)N * d1 * 4), 0x00020000);
-      if (q < 2) {
-        for (int job = 0; job < RG * NT; ++job) {
-          const int g = job / NT, t = job % NT;
-          const int n = t * 16 + col, f0 = g * 8 + q * 4;   // four consecutive features of the slice
-          f32x4 av4, dv4, pv4;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            float z = 0.f, dz = 0.f;
-#pragma unroll
-            for (int ww = 0; ww < WAVES; ++ww) {
-              const float *src = s_fu + ((((ww * RG + g) * NT + t) * 2) * 4 + r) * 32 + lane;
-              z += src[0];
-              dz += src[4 * 32];
-            }
-            const int j = min(jA + f0 + r, d1 - 1);
-            float dphi;
-            const float aval = act_apply(p.act1, z + (p.b1 ? p.b1[j] : 0.f), dphi);
-            av4[r] = aval;
-            pv4[r] = dphi;
-            dv4[r] = dphi * (dz + (p.Vb1 ? p.Vb1[j] : 0.f));
-          }
-          if (n < N && f0 < nf1) {   // (nf1 is a multiple of 4: the quad is all in or all out)
-            const long off = (long)n * d1 + jA + f0;
-            mfu_st_sc1(ra, off, av4);
-            mfu_st_sc1(rd, off, dv4);
-            mfu_st_sc1(rp, off, pv4);
-          }
-        }
-      }
-      MFU_STAMP(3);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every write-through store of this wave acknowledged
-      __builtin_amdgcn_wave_barrier();
-      MFU_STAMP(4);
-      if (lane == 0) {
-        __hip_atomic_fetch_add(c_col, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        unsigned spins = 0, bad = 0u;
-        for (;;) {
-          const unsigned seen = __hip_atomic_load(c_col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if ((int)(seen - target) >= 0) break;
-          __builtin_amdgcn_s_sleep(1);
-          ++spins;
-          if ((spins & 255u) == 0u && __hip_atomic_load(c_err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { bad = 1u; break; }
-          if (spins > p.spin_limit) {   // the grid is not co-resident: end the launch (NaN-marked below), raise the fault word
-            __hip_atomic_store(c_err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (p.fault) __hip_atomic_store(p.fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            bad = 1u;
-            break;
-          }
-        }
-        s_flag = bad;
-      }
-      MFU_STAMP(5);
-    }
-    __syncthreads();
-  }
-  MFU_STAMP(6);
-  const unsigned launch_bad = s_flag;
-  // ---- the [a1 ; da1] operand of the K range: requested FIRST (write-through data: sc1 loads, no L1), then the rest of the
-  // tile chunk; rows [0, NP) = a1, [NP, 2 NP) = da1 (one array at a time: the buffer resource is wave-uniform)
-  {
-    const int q4 = kr >> 2, tot = NP * q4;
-    f32x4 sv[2][SPC];
-#pragma unroll
-    for (int which = 0; which < 2; ++which)
-#pragma unroll
-      for (int u = 0; u < SPC; ++u) {
-        const int e = min(tid + u * MFU_T, tot - 1);
-        const int n = e / q4, kk = (e - n * q4) * 4;
-        sv[which][u] = mfu_ld_sc1(which ? rd : ra, (long)min(n, N - 1) * d1 + k0 + kk);
-      }
-    if (wave != XW) {
-#pragma unroll
-      for (int st = PRE; st < MFU_MAXS; ++st) {
-        tw[st] = CLO_LDW(pW0 + min(st, ns - 1) * 16);
-        tv[st] = CLO_LDW(pV0 + min(st, ns - 1) * 16);
-      }
-    } else {
-#pragma unroll
-      for (int st = 0; st < MFU_MAXS; ++st) {
-        tw[st] = CLO_LDW(pW0 + min(st, ns - 1) * 16);
-        tv[st] = CLO_LDW(pV0 + min(st, ns - 1) * 16);
-      }
-    }
-#pragma unroll
-    for (int which = 0; which < 2; ++which)
-#pragma unroll
-      for (int u = 0; u < SPC; ++u) {
-        const int e = tid + u * MFU_T;
-        if (e < tot) {
-          const int n = e / q4, kk = (e - n * q4) * 4;
-          *reinterpret_cast<f32x4 *>(&s_fu[(which * NP + n) * LDB + kk]) = n < N ? sv[which][u] : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-      }
-  }
-  MFU_STAMP(7);
-  __syncthreads();
-  MFU_STAMP(8);
-  // =====================================================================================
-  // phase 2: partial z2 / dz2 of tile (fb, kb): wave `wave` owns chunks wave, wave + 8 of the block; a chunk's fragments
-  // (<= 11 steps x [W row ; V row]) live in registers, the next chunk's are requested step by step as this one's are used
-  // =====================================================================================
-  const float *pBa = s_fu + idx * LDB + s4;
-  const float *pBd = s_fu + (NP + idx) * LDB + s4;
-  const int q = lane >> 4, col = lane & 15;
-  for (int ch = wave; ch < nch; ch += WAVES) {
-    const bool has_next = ch + WAVES < nch;
-    const float *pWn, *pVn;
-    rows_of(has_next ? ch + WAVES : ch, pWn, pVn);
-    f32x4 accz[NT], accd[NT], accv[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      accz[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-      accd[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-      accv[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int st = 0; st < MFU_MAXS; ++st) {
-      if (st < ns) {
-        const float4 wv = tw[st], vv = tv[st];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          const float4 ba = ld4(pBa + t * 16 * LDB + st * 16);
-          const float4 bd = ld4(pBd + t * 16 * LDB + st * 16);
-#define CLO_MFU_MM(E)                                                                 \
-  accz[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.E, ba.E, accz[t], 0, 0, 0);      \
-  accd[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.E, bd.E, accd[t], 0, 0, 0);      \
-  accv[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(vv.E, ba.E, accv[t], 0, 0, 0);
-          CLO_MFU_MM(x) CLO_MFU_MM(y) CLO_MFU_MM(z) CLO_MFU_MM(w)
-#undef CLO_MFU_MM
-        }
-      }
-      if (has_next) {   // (wave-uniform) the slot just used takes the same step of the wave's next chunk
-        tw[st] = CLO_LDW(pWn + min(st, ns - 1) * 16);
-        tv[st] = CLO_LDW(pVn + min(st, ns - 1) * 16);
-      }
-    }
-    MFU_STAMP(ch == wave ? 9 : 10);
-    // D layout: row = (lane >> 4) * 4 + r = feature inside the chunk, col = batch row in the tile
-    const int j = (c0 + ch) * 16 + q * 4;
-    if (j < d2) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        float *dst = p.part + (((long)kb * 2) * NP + t * 16 + col) * d2 + j;
-        st4(dst, make_float4(accz[t][0], accz[t][1], accz[t][2], accz[t][3]));
-        st4(dst + (long)NP * d2, make_float4(accd[t][0] + accv[t][0], accd[t][1] + accv[t][1],
-                                              accd[t][2] + accv[t][2], accd[t][3] + accv[t][3]));
-      }
-    }
-  }
-  MFU_STAMP(11);
-  __syncthreads();
-  if (tid == 0) {
-    // a launch whose wait was cut short says so in its own output (the slab entry this thread wrote itself)
-    if (launch_bad != 0u && nch > 0) p.part[(((long)kb * 2) * NP) * d2 + (long)c0 * 16] = __builtin_nanf("");
-    __hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(sy), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-}  // namespace clo
-
-static bool mid_fused_shape_ok(int L, const int *dims, int N) {
-  if (L != 3 || N <= NB || N > 64) return false;
-  const int d0 = dims[0], d1 = dims[1], d2 = dims[2];
-  if (d0 % 16 || d1 % 16 || d2 % 4 || d0 < 64 || dims[3] > HEAD_CMAX) return false;
-  if (d1 < 256 || cdiv(d1 / 16, 16) > MFU_MAXS) return false;        // K ranges of 1 .. 11 steps
-  if (d2 < 256 || cdiv(cdiv(d2, 16), 16) > MFU_MAXCH) return false;  // feature blocks of <= 11 chunks
-  return true;
-}
-template <int NT>
-static size_t mid_fused_smem() {
-  const size_t p1 = (size_t)8 * 2 * NT * 2 * 4 * 32, p2 = (size_t)2 * 16 * NT * (MFU_KR + 4);
-  return std::max(p1, p2) * sizeof(float);
-}
-// admission: the column-group counters need all 256 workgroups resident (one per CU), a host-visible fault word, 16-byte
-// aligned operands; otherwise the two-launch route serves
-template <int NT>
-static bool mid_fused_ok(int L, const int *dims, int N, const float *const *W, const float *const *VW, const float *X,
-                         const unsigned *sync) {
-  // BUILT, parity-green and MEASURED in round 6, OFF by default: 27.5 / 40.4 / 50.4 / 64.6 us at 16 / 32 / 48 / 64 rows against
-  // 25.2 / 37 / 51 / 60.5 us for the two launches it replaces (profiles/r06_c2_mid_fused_forward_timeline.txt: the phases of one
-  // workgroup per CU run back to back -- layer 1, slice epilogue, seam, operand staging, tile products -- where two launches
-  // with two workgroups per CU hide each other's prologues).
-#ifndef CLO_MLP_MID_FUSED
-#define CLO_MLP_MID_FUSED 0
-#endif
-  static const bool on = CLO_MLP_MID_FUSED != 0;
-  if (!on || !sync || !mid_fused_shape_ok(L, dims, N)) return false;
-  if (!W[0] || !VW[0] || !W[1] || !VW[1]) return false;
-  for (const void *q : {(const void *)W[0], (const void *)VW[0], (const void *)W[1], (const void *)VW[1], (const void *)X})
-    if (!aligned16(q)) return false;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  if (device_cu_count(dev) != MFU_G) return false;
-  if (!fault_words_device(dev) || fault_disabled(dev, FAULT_MEGA)) return false;
-  static int occ[64];
-  static std::once_flag once;
-  std::call_once(once, [] { for (int &o : occ) o = -1; });
-  int o = __atomic_load_n(&occ[dev], __ATOMIC_RELAXED);
-  if (o < 0) {
-    int nb = 0;
-    const void *fn = reinterpret_cast<const void *>(mid_fused_fwd_kernel<NT>);
-    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mid_fused_smem<NT>());
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, MFU_T, mid_fused_smem<NT>()) != hipSuccess) {
-      (void)hipGetLastError();
-      nb = 0;
-    }
-    o = nb >= 1 ? 1 : 0;
-    __atomic_store_n(&occ[dev], o, __ATOMIC_RELAXED);
-  }
-  return o == 1;
-}
-template <int NT>
-static int mid_fused_launch(const MidFusedArgs &a0, hipStream_t st) {
-  MidFusedArgs a = a0;
-  int dev = 0;
-  int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
-  if (rc != CLO_OK) return rc;
-  a.fault = fault_words_device(dev);
-  if (a.fault) a.fault += FAULT_MEGA;
-  a.spin_limit = spin_limit();
-  PersistGate &gate = PersistGate::of(dev);
-  rc = gate.admit(st, MFU_G);
-  if (rc != CLO_OK) return rc;
-  {
-    ProfScope prof(0, 8.0 * ((double)a.d0 * a.d1 + (double)a.d1 * a.d2), st);
-    hipLaunchKernelGGL((mid_fused_fwd_kernel<NT>), dim3(MFU_G), dim3(MFU_T), mid_fused_smem<NT>(), st, a);
-  }
-  rc = check_hip(hipGetLastError(), "mid_fused_fwd_kernel");
-  if (rc != CLO_OK) {
-    gate.abort();
-    return rc;
-  }
-  return gate.done(st);
-}
 
 constexpr int MID_MAX_N = 64;
 
 static bool mid_chain_ok(int L, const int *dims, const float *const *W, const float *const *VW,
                          float *const *OW, int N) {
-#ifndef CLO_MLP_NO_MID
-#define CLO_MLP_NO_MID 0
-#endif
-  static const bool off = CLO_MLP_NO_MID != 0;
-  if (off || N <= NB || N > MID_MAX_N || L < 2 || L > OUTER_MAXL) return false;
+  if (N <= NB || N > MID_MAX_N || L < 2 || L > OUTER_MAXL) return false;
   for (int l = 1; l <= L - 1; ++l)
     if (dims[l - 1] % 4 != 0 || dims[l] % 4 != 0 || dims[l - 1] < 16 || !aligned16(W[l - 1]) ||
         !aligned16(VW[l - 1]) || !aligned16(OW[l - 1]))
@@ -3828,7 +3342,7 @@ static int mid_chain(int L, const int *dims, const int *acts, const float *const
                      const float *const *b, const float *const *VW, const float *const *Vb,
                      float *const *OW, float *const *Ob, int N, int loss_kind, const float *aux,
                      int aux_rank, float scale, float beta, float *const *a, float *const *da,
-                     float *const *dphi, float *const *dl, float *gws, long gws_sz, unsigned *fsync, hipStream_t st) {
+                     float *const *dphi, float *const *dl, float *gws, long gws_sz, hipStream_t st) {
   constexpr int NP = 16 * NT;
   int dmax = 0;
   for (int l = 0; l <= L; ++l) dmax = std::max(dmax, dims[l]);
@@ -3847,68 +3361,29 @@ static int mid_chain(int L, const int *dims, const int *acts, const float *const
   float *dslab[2] = {dLbuf + dL_sz, dLbuf + dL_sz + JB_MAX * NP * dmax};
   if (fslab_sz + hp_sz + dL_sz + 2 * JB_MAX * NP * dmax > gws_sz) return CLO_EUNSUP;
   int rc;
-  // ---- forward + JVP of layers 1 and 2 in ONE persistent launch where the network and the device allow it
-  int l_first = 1;
-  if (mid_fused_ok<NT>(L, dims, N, W, VW, a[0], fsync)) {
-    MidFusedArgs fa{};
-    fa.W1 = W[0]; fa.b1 = b ? b[0] : nullptr; fa.V1 = VW[0]; fa.Vb1 = Vb ? Vb[0] : nullptr; fa.X = a[0];
-    fa.W2 = W[1]; fa.V2 = VW[1];
-    fa.a1 = a[1]; fa.da1 = da[1]; fa.dphi1 = dphi[1]; fa.part = fslab;
-    fa.N = N; fa.d0 = dims[0]; fa.d1 = dims[1]; fa.d2 = dims[2]; fa.act1 = acts[0];
-    fa.sync = fsync;
-    rc = mid_fused_launch<NT>(fa, st);
-    if (rc != CLO_OK) return rc;
-    {  // finish layer 2 (16 K ranges) + partial products of the head: as behind mid_fwd_kernel
-      HeadFwdArgs ha{};
-      ha.part = fslab; ha.ksplit = 16; ha.part_rows = NP;
-      ha.b = b ? b[1] : nullptr; ha.Vb = Vb ? Vb[1] : nullptr;
-      ha.a = a[2]; ha.da = da[2]; ha.dphi = dphi[2];
-      ha.N = N; ha.d = dims[2]; ha.act = acts[1];
-      ha.WL = W[L - 1]; ha.VL = VW[L - 1]; ha.C = C; ha.hp = hp;
-      ProfScope pf(3, 0.0, st);
-      hipLaunchKernelGGL(head_fwd_kernel, dim3(head_nblk, N), dim3(256), 0, st, ha);
-      CLO_CHECK_LAUNCH("head_fwd_kernel");
-    }
-    l_first = L;   // (L == 3: both hidden layers are done)
-  }
   // ---- forward + JVP: hidden layers 1 .. L-1
-  for (int l = l_first; l <= L - 1; ++l) {
+  for (int l = 1; l <= L - 1; ++l) {
     const int di = dims[l - 1], dout = dims[l];
     const bool has_da = l > 1;
     // Layers without an incoming tangent (the first one) finish in their own launch (in-block split-K over the
     // 8 waves: no slabs, no finish launch: -2...4 us).  With a tangent the kernel issues twice the B loads per
     // weight load and measured slower than the slab route (C2 layer 2: 24.8 vs 17.9 us at 16 rows, 67 vs 46 us
-    // at 64); CLO_MLP_MID_FULL_DA=1 forces it.
-#ifndef CLO_MLP_NO_MID_FULL
-#define CLO_MLP_NO_MID_FULL 0
-#endif
-    static const bool no_full = CLO_MLP_NO_MID_FULL != 0;
-#ifndef CLO_MLP_MID_FULL_DA
-#define CLO_MLP_MID_FULL_DA 0
-#endif
-    static const bool full_da = CLO_MLP_MID_FULL_DA != 0;
-    if (!no_full && (!has_da || full_da) && di >= 256 && cdiv(dout, 16) >= kNumCU / 2) {
+    // at 64).
+    if (!has_da && di >= 256 && cdiv(dout, 16) >= kNumCU / 2) {
       const int kpw = (int)cdiv(cdiv(di, 8), 16) * 16;
       const int fpb = (int)std::min<long>(16, std::max<long>(4, cdiv(dout, kNumCU)));
       const size_t smem = (size_t)8 * 2 * NT * 2 * 4 * 32 * sizeof(float);
       {
         ProfScope prof(0, 8.0 * di * dout, st);
-#define CLO_MIDFULL(DA, UU)                                                                                   \
-  rc = set_smem(mid_full_kernel<NT, DA, UU>, smem);                                                           \
+#define CLO_MIDFULL(UU)                                                                                       \
+  rc = set_smem(mid_full_kernel<NT, false, UU>, smem);                                                        \
   if (rc != CLO_OK) return rc;                                                                                \
-  hipLaunchKernelGGL((mid_full_kernel<NT, DA, UU>), dim3((unsigned)cdiv(dout, fpb)), dim3(512), smem, st,     \
+  hipLaunchKernelGGL((mid_full_kernel<NT, false, UU>), dim3((unsigned)cdiv(dout, fpb)), dim3(512), smem, st,  \
                      W[l - 1], b ? b[l - 1] : nullptr, VW[l - 1], Vb ? Vb[l - 1] : nullptr, a[l - 1],         \
-                     DA ? da[l - 1] : nullptr, a[l], da[l], dphi[l], N, di, dout, acts[l - 1], kpw, fpb)
-        if (!has_da) {
-#ifndef CLO_MID_FULL_U8
-#define CLO_MID_FULL_U8 1
-#endif
-          // (all eight k steps of a wave in ONE batch of loads: a single memory round trip; round 6: also at 33 ... 48 rows, -1 ... -2 us;
-          // at 49 ... 64 rows the batch needs 250 registers per lane and measures 1 - 1.5 us slower than two batches of four)
-          if (kpw == 128 && di % 128 == 0 && (NT <= 2 || (CLO_MID_FULL_U8 && NT == 3))) { CLO_MIDFULL(false, 8); } else { CLO_MIDFULL(false, 4); }
-        } else {
-          if (NT <= 2) { CLO_MIDFULL(true, 4); } else { CLO_MIDFULL(true, 2); }
-        }
+                     nullptr, a[l], da[l], dphi[l], N, di, dout, acts[l - 1], kpw, fpb)
+        // (all eight k steps of a wave in ONE batch of loads: a single memory round trip; round 6: also at 33 ... 48 rows, -1 ... -2 us;
+        // at 49 ... 64 rows the batch needs 250 registers per lane and measures 1 - 1.5 us slower than two batches of four)
+        if (kpw == 128 && di % 128 == 0 && NT <= 3) { CLO_MIDFULL(8); } else { CLO_MIDFULL(4); }
 #undef CLO_MIDFULL
         CLO_CHECK_LAUNCH("mid_full_kernel");
       }
@@ -3933,18 +3408,10 @@ static int mid_chain(int L, const int *dims, const int *acts, const float *const
     int wv = 4;
     long ksplit = 1, kpb = 32;
     double best = 1e300;
-#ifndef CLO_MLP_MID_WV
-#define CLO_MLP_MID_WV 0
-#endif
-#ifndef CLO_MID_KGRAN16
-#define CLO_MID_KGRAN16 0   // (measured neutral, same box: 64 rows 117.5 vs 117.2 us)
-#endif
     for (int w : {4, 8}) {
-      if (CLO_MLP_MID_WV && w != CLO_MLP_MID_WV) continue;   // (A/B builds: force the waves per block)
       const long rb = cdiv(dout, w * 16);
       for (long ks = 1; ks <= KS_MAX; ++ks) {
-        const long kgran = (NT >= 3 && CLO_MID_KGRAN16) ? 16 : 32;   // (MFMA-bound beyond 32 rows: the finer K ranges fill the chip -- 21 x 12 blocks instead of 21 x 11)
-        const long kp = cdiv(cdiv(di, ks), kgran) * kgran;
+        const long kp = cdiv(cdiv(di, ks), 32) * 32;   // (16-column K ranges beyond 32 rows measured neutral: 64 rows 117.5 vs 117.2 us)
         if (kp > kpb_max) continue;
         const long kse = cdiv(di, kp);
         const long blocks = rb * kse;
@@ -4018,24 +3485,15 @@ static int mid_chain(int L, const int *dims, const int *acts, const float *const
     hipLaunchKernelGGL(head_bwd_rows_kernel, dim3(head_nblk, (unsigned)cdiv(N, NB)), dim3(256), 0, st, ba, dLbuf);
     CLO_CHECK_LAUNCH("head_bwd_rows_kernel");
   }
-  // ---- data chain delta_{l-1} = delta_l W_l for l = L-1 .. 2, each step merged with the outer products that need delta_l
-  // only (layer l; at the first step also the head's layer L); the last launch forms the remaining outer products
-#ifndef CLO_MID_OCW128
-#define CLO_MID_OCW128 0
-#endif
-  constexpr int OCW = (NT <= 2 && !CLO_MID_OCW128) ? 256 : 128;
+  // ---- data chain delta_{l-1} = delta_l W_l for l = L-1 .. 2; then the outer products of every layer in one launch
+  constexpr int OCW = NT <= 2 ? 256 : 128;
   const size_t osmem = (size_t)NP * (MIDO_ROWS + 16 + OCW) * sizeof(float);
-  // (MEASURED in round 6 and left OFF: the merged launch is 0.5 - 3 us SLOWER at every row count, profiles/
-  // r06_c2_mid_merged_backward_ab.txt -- a read-only sweep and a write-only stream sharing the chip slow each other down by
-  // more than the saved boundary, as round 1 found for a kernel that did both per tile)
-#ifndef CLO_MLP_MID_MERGE
-#define CLO_MLP_MID_MERGE 0
-#endif
-  static const bool merge_on = CLO_MLP_MID_MERGE != 0;
+  // (a launch that merged each step with the outer products that only need delta_l measured 0.5 - 3 us SLOWER at every row
+  // count, profiles/r06_c2_mid_merged_backward_ab.txt -- a read-only sweep and a write-only stream sharing the chip slow each
+  // other down by more than the saved boundary, as round 1 found for a kernel that did both per tile)
   MidDelta md[OUTER_MAXL + 2];
   md[L - 1] = MidDelta{dl[L - 1], nullptr, nullptr, 0, 0};
   md[L] = MidDelta{dLbuf, nullptr, nullptr, 0, HEAD_CMAX};  // the head's delta, [N][HEAD_CMAX]
-  bool outer_done[OUTER_MAXL + 2] = {};
   auto outer_args = [&](const int *layers, int count, MidOuterArgs &oa, double &bytes) {
     oa = MidOuterArgs{};
 #ifdef CLO_MID_TIMING
@@ -4060,21 +3518,12 @@ static int mid_chain(int L, const int *dims, const int *acts, const float *const
     const int di = dims[l - 1], dout = dims[l];
     // (beyond 32 rows a block's delta rows and merge buffer leave room for ONE block per CU: the grid must not exceed the CUs --
     // round 6: JB_MAX was 12 there, C2's layer 2 ran on 11 x 12 = 132 of the 256 CUs, 28.8 us at 64 rows)
-#ifndef CLO_MID_DPREV_CQ2
-#define CLO_MID_DPREV_CQ2 1
-#endif
     // (beyond 32 rows, round 6: blocks of 128 columns x 4 row quarters -- the same number of blocks with half the row ranges, i. e.
     // half the slabs this launch writes and the finish launch reads)
-#ifndef CLO_MID_DPREV_CQ2_ALL
-#define CLO_MID_DPREV_CQ2_ALL 0
-#endif
-    constexpr int DCQ = ((NT >= 3 || CLO_MID_DPREV_CQ2_ALL) && CLO_MID_DPREV_CQ2 && !CLO_MLP_MID_MERGE) ? 2 : 4;
+    constexpr int DCQ = NT >= 3 ? 2 : 4;
     constexpr int DCOLS = 64 * DCQ;
-#ifndef CLO_MID_DPREV_FLOOR
-#define CLO_MID_DPREV_FLOOR 1
-#endif
     // (never more blocks than CUs: 11 x 24 = 264 blocks left eight CUs with two blocks each -- twice the time of the other 248)
-    long JB = (NT <= 2 && !CLO_MID_DPREV_FLOOR) ? cdiv(kNumCU, cdiv(di, DCOLS)) : std::max<long>(1, kNumCU / cdiv(di, DCOLS));
+    long JB = std::max<long>(1, kNumCU / cdiv(di, DCOLS));
     JB = std::min<long>({JB, cdiv(dout, 64), JB_MAX});
     JB = std::max<long>(JB, cdiv(dout, NT <= 2 ? 512 : 256));   // LDS: rows x (Npad + 16) delta + merge buffer
     const int rpb = (int)(cdiv(cdiv(dout, JB), 8) * 8);
@@ -4088,42 +3537,14 @@ static int mid_chain(int L, const int *dims, const int *acts, const float *const
 #ifdef CLO_MID_TIMING
     dq.stamps = g_mid_stamps_host; dq.gx = gx;
 #endif
-    if (merge_on) {
-      int layers[2] = {l, L};
-      const int count = l == L - 1 ? 2 : 1;
-      MidOuterArgs oa;
-      double obytes;
-      const int nbo = outer_args(layers, count, oa, obytes);
-      const size_t msmem = std::max(smem, osmem);
-      ProfScope prof(2, 4.0 * di * dout + obytes, st);
-      if (beta != 0.f) {
-        rc = set_smem(mid_bwd_merged_kernel<NT, true, OCW>, msmem);
-        if (rc != CLO_OK) return rc;
-        hipLaunchKernelGGL((mid_bwd_merged_kernel<NT, true, OCW>), dim3((unsigned)(gx * JBe + nbo)), dim3(512), msmem, st, dq,
-                           oa, gx * JBe, gx);
-      } else {
-        rc = set_smem(mid_bwd_merged_kernel<NT, false, OCW>, msmem);
-        if (rc != CLO_OK) return rc;
-        hipLaunchKernelGGL((mid_bwd_merged_kernel<NT, false, OCW>), dim3((unsigned)(gx * JBe + nbo)), dim3(512), msmem, st, dq,
-                           oa, gx * JBe, gx);
-      }
-      CLO_CHECK_LAUNCH("mid_bwd_merged_kernel");
-      outer_done[l] = true;
-      if (count == 2) outer_done[L] = true;
-    } else {
+    {
       rc = set_smem(mid_dprev_kernel<NT, DCQ>, smem);
       if (rc != CLO_OK) return rc;
       ProfScope prof(2, 4.0 * di * dout, st);
       hipLaunchKernelGGL((mid_dprev_kernel<NT, DCQ>), dim3((unsigned)gx, (unsigned)JBe), dim3(512), smem, st, dq);
       CLO_CHECK_LAUNCH("mid_dprev_kernel");
     }
-#ifndef CLO_MID_NT2_STREAM
-#define CLO_MID_NT2_STREAM 0
-#endif
-#ifndef CLO_MID_FINISH_MIN_NT
-#define CLO_MID_FINISH_MIN_NT 3
-#endif
-    if (!fin && (NT >= CLO_MID_FINISH_MIN_NT || (NT == 2 && CLO_MID_NT2_STREAM))) {   // one pass over the slabs instead of one per consumer block
+    if (!fin && NT >= 3) {   // one pass over the slabs instead of one per consumer block
       const long total4 = (long)N * di / 4;
       hipLaunchKernelGGL(mid_delta_finish_kernel, dim3((unsigned)cdiv(total4, 256)), dim3(256), 0, st, slab, JBe,
                          (long)NP * di, dphi[l - 1], dl[l - 1], total4);
@@ -4133,24 +3554,20 @@ static int mid_chain(int L, const int *dims, const int *acts, const float *const
       md[l - 1] = fin ? MidDelta{dl[l - 1], nullptr, nullptr, 0, 0} : MidDelta{nullptr, slab, dphi[l - 1], JBe, 0};
     }
   }
-  // ---- the outer products not formed yet (layer 1; every layer of a two-layer net), one launch
+  // ---- the outer products of every layer, one launch
   {
     int layers[OUTER_MAXL + 1];
-    int count = 0;
-    for (int l = 1; l <= L; ++l)
-      if (!outer_done[l]) layers[count++] = l;
+    const int count = L;
+    for (int l = 1; l <= L; ++l) layers[l - 1] = l;
     MidOuterArgs oa;
     double bytes;
     const int nb = outer_args(layers, count, oa, bytes);
     ProfScope prof(4, bytes, st);
-#ifndef CLO_MLP_MID_OUTER2
-#define CLO_MLP_MID_OUTER2 1
-#endif
     bool aligned4 = true;
     for (int k = 0; k < count; ++k) aligned4 = aligned4 && dims[layers[k] - 1] % 4 == 0;
     // (measured: at <= 32 rows the tile-per-block kernel is 1.5 - 7 us faster -- its blocks are short there and delta_1 still
     // arrives as row-range slabs that every block would sum again; from 33 rows on the streaming form wins)
-    if (CLO_MLP_MID_OUTER2 && aligned4 && (NT >= 3 || (NT == 2 && CLO_MID_NT2_STREAM))) return launch_mid_outer2<NT>(oa, count, beta, N, st);
+    if (aligned4 && NT >= 3) return launch_mid_outer2<NT>(oa, count, beta, N, st);
     rc = beta != 0.f ? set_smem(mid_outer_kernel<NT, true, OCW>, osmem)
                      : set_smem(mid_outer_kernel<NT, false, OCW>, osmem);
     if (rc != CLO_OK) return rc;
@@ -4201,16 +3618,12 @@ static long ggn_ws_mega_offset(int L, const int *dims, int N) {
 }
 extern "C" long clo_mlp_ggn_ws_floats(int L, const int *dims, int N) {
   if (L <= 0 || !dims || N < 0) return 0;
-  if (mid_fused_shape_ok(L, dims, N)) return ggn_ws_mega_offset(L, dims, N) + MFU_SYNC_WORDS;
   if (!mega_shape_ok(L, dims, N)) return ggn_ws_core_floats(L, dims, N);
   return ggn_ws_mega_offset(L, dims, N) + cdiv(mega_xch_floats(dims[1], dims[2]), 64) * 64 + mega_sync_words() +
          mega_debug_floats();
 }
 extern "C" int clo_mlp_ggn_ws_init(int L, const int *dims, int N, float *ws, void *stream) {
   CLO_REQUIRE(L >= 1 && dims && N >= 0 && ws, "clo_mlp_ggn_ws_init: bad arguments");
-  if (mid_fused_shape_ok(L, dims, N))   // counters of the fused two-layer forward of the 9 ... 64-row chain
-    return check_hip(hipMemsetAsync(ws + ggn_ws_mega_offset(L, dims, N), 0, (size_t)MFU_SYNC_WORDS * 4, (hipStream_t)stream),
-                     "hipMemsetAsync(fused forward counters)");
   if (!mega_shape_ok(L, dims, N)) return CLO_OK;  // nothing to initialise
   // the counters AND the exchange area: its tagged slots (CLO_MG_TOPLL in mlp_mega.hip) must not show a tag of some earlier
   // owner of this memory
@@ -4320,17 +3733,10 @@ extern "C" int clo_mlp_ggn_matvec(int L, const int *dims, const int *acts, const
                        xch, sync, st);
   }
   if (narrow && mid_chain_ok(L, dims, W, VW, OW, N)) {
-    // counters of the fused two-layer forward (behind the core workspace, zeroed by clo_mlp_ggn_ws_init)
-    unsigned *fsync = mid_fused_shape_ok(L, dims, N) ? reinterpret_cast<unsigned *>(ws + ggn_ws_mega_offset(L, dims, N)) : nullptr;
 #define CLO_MID_CHAIN(T)                                                                              \
   mid_chain<T>(L, dims, acts, W, b, VW, Vb, OW, Ob, N, loss_kind, aux, aux_rank, loss_scale * alpha, beta, \
-               a, da, dphi, dl, gws, gws_sz, fsync, st)
-#ifndef CLO_MLP_MID_MAX
-#define CLO_MLP_MID_MAX MID_MAX_N
-#endif
-    static const int mid_max = CLO_MLP_MID_MAX;
-    rc = N > mid_max ? CLO_EUNSUP
-         : N <= 16 ? CLO_MID_CHAIN(1) : N <= 32 ? CLO_MID_CHAIN(2) : N <= 48 ? CLO_MID_CHAIN(3) : CLO_MID_CHAIN(4);
+               a, da, dphi, dl, gws, gws_sz, st)
+    rc = N <= 16 ? CLO_MID_CHAIN(1) : N <= 32 ? CLO_MID_CHAIN(2) : N <= 48 ? CLO_MID_CHAIN(3) : CLO_MID_CHAIN(4);
 #undef CLO_MID_CHAIN
     if (rc != CLO_EUNSUP) return rc;
   }
@@ -4416,11 +3822,7 @@ extern "C" int clo_mlp_ggn_matvec(int L, const int *dims, const int *acts, const
       rc = launch_loss(loss_kind, a[L], aux, aux_rank, da[L], nullptr, dl0, N, C, loss_scale * alpha,
                        nullptr, 1, nullptr, nullptr, a[L], da[L], st);
     if (rc != CLO_OK) return rc;
-#ifndef CLO_HEAD_BACK_FUSED
-#define CLO_HEAD_BACK_FUSED 1
-#endif
-    static const int head_back_fused = CLO_HEAD_BACK_FUSED;
-    if (head_back_fused && N <= HB_FUSE_N && C <= HEAD_CMAX) {   // (256 rows: 317 us with the one launch, 308 with the four)
+    if (N <= HB_FUSE_N && C <= HEAD_CMAX) {   // (256 rows: 317 us with the one launch, 308 with the four)
       const int nbj = (int)cdiv(d, 64);
       hipLaunchKernelGGL(head_rows_back_kernel, dim3((unsigned)(nbj * (1 + cdiv(N, HB_DROWS)))), dim3(HB_GROUPS * 64), 0, st, dl0,
                          a[L - 1], W[L - 1], dphi[L - 1], OW[L - 1], Ob ? Ob[L - 1] : nullptr, dl1, N, d, C, beta, nbj);
@@ -4492,11 +3894,8 @@ extern "C" int clo_mlp_ggn_matvec(int L, const int *dims, const int *acts, const
     return CLO_OK;
   }
   // ---- backward (two 8-row passes / GEMM path): layer by layer
-#ifndef CLO_MLP_ROWS_OUTER2
-#define CLO_MLP_ROWS_OUTER2 1
-#endif
   // (measured up to 192 rows, nine to twelve row tiles, one block per CU: 3 ... 15 us SLOWER than the GEMM engine there)
-  const bool rows_outer2 = CLO_MLP_ROWS_OUTER2 && !skinny && N <= 128;
+  const bool rows_outer2 = !skinny && N <= 128;
   MidOuterArgs pend{};
   pend.alpha = 1.f; pend.beta = beta; pend.N = N;
   auto flush_outer2 = [&]() -> int {
@@ -4713,10 +4112,6 @@ static int mlp_matmat_impl(const char *what, int L, const int *dims, const int *
   }
   const int G = K / 4, FPT = 16 / G;
   const bool last_linear = acts[L - 1] == CLO_ACT_IDENTITY;
-#ifndef CLO_KC_LAST
-#define CLO_KC_LAST 1
-#endif
-  static const int kc_last = CLO_KC_LAST;   // narrow last layer: klast_* kernels instead of GEMM engine + weight stream
 
   for (int n0 = 0; n0 < N; n0 += NB) {
     const int nn = std::min(NB, N - n0);
@@ -4730,7 +4125,7 @@ static int mlp_matmat_impl(const char *what, int L, const int *dims, const int *
                         nullptr, dphi[l], nn, di, dout, acts[l - 1], part, false, nullptr, st);
       if (rc != CLO_OK) return rc;
       const int klast_slabs = (int)cdiv(di, KL_ROWS);
-      if (kc_last && l == L && l >= 2 && dout <= KL_CMAX && nn * G <= 128 &&
+      if (l == L && l >= 2 && dout <= KL_CMAX && nn * G <= 128 &&
           (long)klast_slabs * dout * NK <= gws_sz) {   // narrow last layer: tangent GEMM + weight stream in one pass
         const float *dpl = last_linear ? nullptr : dphi[l];
         if (nn * G <= 64)
@@ -4750,10 +4145,7 @@ static int mlp_matmat_impl(const char *what, int L, const int *dims, const int *
         rc = launch_gemm_auto(g, gws, gws_sz, st);
         if (rc != CLO_OK) return rc;
       }
-#ifndef CLO_KC_BPC
-#define CLO_KC_BPC 4
-#endif
-      static const int kc_bpc = CLO_KC_BPC;
+      constexpr int kc_bpc = 4;
       // equal tile counts per block: with `slots` blocks in flight ceil(tiles / slots) rounds of tiles are needed anyway, so
       // the tiles are dealt to tiles / rounds blocks (d_out = 2688, K = 32: 1344 tiles on 672 blocks x 2 instead of 1024
       // blocks with 1 or 2; 96.8 -> 92.6 us per launch)
@@ -4814,12 +4206,8 @@ static int mlp_matmat_impl(const char *what, int L, const int *dims, const int *
       {
         ProfScope prof(4, 4.0 * di * dout * K * (bw != 0.f ? 2 : 1), st);
         float *ob = Ob ? Ob[l - 1] : nullptr;
-#ifndef CLO_KO_TRIPS
-#define CLO_KO_TRIPS 1
-#endif
-        // rows of a chunk: CLO_KO_TRIPS trips of 16 wave instructions = 16 KB each (0: the whole input range per block)
-        const int trip_rows = 4 * CLO_KO_U * (64 / (K >> 2));
-        const int chunk_rows = CLO_KO_TRIPS > 0 ? CLO_KO_TRIPS * trip_rows : di;
+        // rows of a chunk: one trip of 16 wave instructions = 16 KB
+        const int chunk_rows = 4 * KO_U * (64 / (K >> 2));
         const int nchunk = (int)cdiv(di, chunk_rows);
         const dim3 kgrid((unsigned)((long)dout * nchunk));
         if (bw != 0.f)
@@ -4830,7 +4218,7 @@ static int mlp_matmat_impl(const char *what, int L, const int *dims, const int *
                              ob, aT[l - 1], dA[l], nn, K, di, bw, bt, nchunk, chunk_rows);
         CLO_CHECK_LAUNCH("kouter_stream_kernel");
       }
-      if (l >= 2 && !Gh && kc_last && l == L && dout <= KL_CMAX) {
+      if (l >= 2 && !Gh && l == L && dout <= KL_CMAX) {
         const long quads = (long)di * (NK >> 2);
         hipLaunchKernelGGL(klast_delta_kernel, dim3((unsigned)std::min<long>(cdiv(quads, 256), 8L * kNumCU)), dim3(256), 0, st,
                            W[l - 1], dA[l], dphi[l - 1], dA[l - 1], nn, K, di, dout);
@@ -4941,11 +4329,7 @@ extern "C" int clo_mlp_hessian_matvec(int L, const int *dims, const int *acts, c
     part_sz = std::max({part_sz, clo_mlp_bwd_ws_floats(N, dims[l - 1], dims[l]),
                         clo_mlp_fwd_ws_floats(N, dims[l - 1], dims[l])});
   part_sz = (part_sz + 3) & ~3L;
-#ifndef CLO_HESSIAN_GEMM
-#define CLO_HESSIAN_GEMM 0
-#endif
-  static const int no_skinny = CLO_HESSIAN_GEMM;
-  const bool skinny = N <= SKINNY_MAX_N && !no_skinny && 3 * part_sz + 2 * nd <= gws_sz;
+  const bool skinny = N <= SKINNY_MAX_N && 3 * part_sz + 2 * nd <= gws_sz;
   float *part = gws, *part2 = gws + part_sz, *part3 = gws + 2 * part_sz, *ones = gws + 3 * part_sz, *T2b = ones + nd;
   if (skinny) {
     hipLaunchKernelGGL(fill_kernel, dim3(ew_grid(nd)), dim3(256), 0, st, ones, nd, 1.f);

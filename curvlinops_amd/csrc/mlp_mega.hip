@@ -47,21 +47,6 @@ constexpr int MG_KR = MG_MAXS * 16;      // 176 columns per K range
 constexpr int MG_LDW = 176;              // row pitch of the W2 tile in LDS (= 16 mod 32: conflict-free b32 column reads)
 constexpr int MG_LDB = MG_KR + 4;        // row pitch of the staged [a1 ; da1] operand
 constexpr int MG_P1S = 8;                // k16 steps per wave in layer 1 (d0 <= 1024)
-#ifndef CLO_MG_PRE
-#define CLO_MG_PRE 2
-#endif
-#ifndef CLO_MG_PACE
-#define CLO_MG_PACE 3
-#endif
-#ifndef CLO_MG_XCD
-#define CLO_MG_XCD 1
-#endif
-// Skeleton builds (tools/run_mega_skeleton.sh): bit 0 drops the layer-1 / layer-2 MFMAs, bit 1 the delta_1 sweep's FMAs, bit 2
-// the FMAs of out_W2, bit 3 those of out_W1 -- every load, LDS copy, seam and store stays, each loaded value still feeds
-// (one add) what is stored, so the timing is that of the data movement and the exchanges alone; the results are garbage.
-#ifndef CLO_MG_ABLATE
-#define CLO_MG_ABLATE 0
-#endif
 // Scalar memory path at the seams (round 5; tools/ubench/smem_seam_probe.hip, profiles/r05_c2_scalar_seam.txt).  A CU's
 // vector-memory pipe returns in issue order, so a seam's poll and gather wait behind every weight byte requested before
 // them; s_load ... glc goes to L2 on the scalar cache's own path.  Tried and measured on the headline shape:
@@ -69,30 +54,25 @@ constexpr int MG_P1S = 8;                // k16 steps per wave in layer 1 (d0 <=
 //     gather 44.5): the SGPR file holds four 64-byte chunks per wave, so 176 chunks take six ~0.9 us round trips;
 //   * publish with s_store_dwordx4 + s_dcache_wb: correct, 0.8 us slower than the sc1 vector stores;
 //   * POLL and ARRIVE of a counter: faster (below).  That is what is kept.
-// Scalar POLL of group counters, CLO_MG_SPOLL (the gathers stay on the vector path).  A wait is one wave spinning on
+// Scalar POLL of group counters at seam A and on the top flag (the gathers stay on the vector path).  A wait is one wave spinning on
 // s_load_dword ... glc: it neither queues behind the weight loads / write-only stores of its CU nor adds to them.
 // Counters are monotonic within a call and the data is read with sc1 vector loads issued after the poll returned, so the
 // scalar read can only be late, never wrong (every 64th spin also reads the counter the architected way).  Measured per
-// seam (bits below): seam A -1.2 us, the fanned-out top flag -0.7 us, the other three nothing; polling ONE top line from
-// all 256 workgroups through the scalar path costs +15 us, hence CLO_MG_TOPFAN.
-#ifndef CLO_MG_SPOLL
-#define CLO_MG_SPOLL 9
-#endif
-constexpr int MG_PRE = CLO_MG_PRE;       // tile steps issued right behind the layer-1 loads
+// seam: seam A -1.2 us, the fanned-out top flag -0.7 us, the other three (rowA, rowB, colB) nothing, so those keep the
+// vector poll; polling ONE top line from all 256 workgroups through the scalar path costs +15 us, hence the fan-out below.
+constexpr int MG_PRE = 2;       // tile steps issued right behind the layer-1 loads
 // round 4: the compute waves keep requesting the layer-2 tile WHILE wave 7 runs the first seam, never
 // more than MG_PACE steps (3 KB per wave and step) ahead of what has landed: the vector-memory pipe of the CU stays busy
 // through the seam, and the seam's gather queues behind <= MG_PACE x 21 KB instead of behind the whole tile.
-constexpr int MG_PACE = CLO_MG_PACE;
+constexpr int MG_PACE = 3;
 // round 5: only the first MG_HOLD steps of the tile are requested before / during seam A; the rest is requested inside
 // phase 2, MG_HOLD steps ahead of its use.  Phase 2 used to start with a wait for the WHOLE tile (the conditional requests
 // made hipcc count conservatively), and the seam's publish / gather queued behind whatever had been requested.  Measured:
 // seam A ends 1.6 us earlier (a1 in LDS at 12.9 instead of 14.5 us), phase 2 ends when it did before (19.9 us) -- it now
 // waits for the held-back steps: the 82 MB of W1, V1, W2, V2 arrive at ~4.2 TB/s whatever the request schedule (16 rows x
 // 64 bytes per request, 704 contiguous bytes per tile row).  MG_HOLD 3 .. 11: 40.8 .. 41.4 us per product.
-#ifndef CLO_MG_HOLD
-#define CLO_MG_HOLD 7
-#endif
-constexpr int MG_HOLD = CLO_MG_HOLD < MG_PRE ? MG_PRE : (CLO_MG_HOLD > MG_MAXS ? MG_MAXS : CLO_MG_HOLD);
+constexpr int MG_HOLD = 7;
+static_assert(MG_PRE <= MG_HOLD && MG_HOLD <= MG_MAXS, "tile steps held back");
 constexpr int MG_NB = 8, MG_CMAX = 16;
 constexpr int MG_MAXDEV = 64;            // device ordinals with per-device launch state
 constexpr unsigned MG_SPIN = 1u << 22;   // bound of every spin (each poll is a fabric round trip + s_sleep)
@@ -149,12 +129,9 @@ __host__ __device__ inline long mg_off_gsum(int d1, int d2) { return mg_off_hp(d
 __host__ __device__ inline long mg_off_slab2(int d1, int d2) { return mg_off_gsum(d1, d2) + 16L * 256; }
 long mega_xch_floats(int d1, int d2) { return mg_off_slab2(d1, d2) + 16L * MG_NB * d1 + 64; }
 // sync words: line 0 = {call, err}; two sets of 65 counters (colA[16], rowA[16], rowB[16], colB[16], top), one per 128-B line
-// The chip-wide "top" flag is fanned out (CLO_MG_TOPFAN): each of the 16 row-group leaders adds to 16 lines (one
+// The chip-wide "top" flag is fanned out: each of the 16 row-group leaders adds to 16 lines (one
 // instruction, lane = line) and a workgroup polls the line of its own row group -- 16 pollers per line instead of 256.
-#ifndef CLO_MG_TOPFAN
-#define CLO_MG_TOPFAN 1
-#endif
-constexpr int MG_SET_LINES = CLO_MG_TOPFAN ? 80 : 65;
+constexpr int MG_SET_LINES = 80;
 long mega_sync_words() { return 32L * (1 + 2 * MG_SET_LINES); }
 // -DCLO_MEGA_TIMING builds stamp wall_clock64() at 16 points per workgroup into the 8192 floats behind the counters
 long mega_debug_floats() { return 16384; }
@@ -199,21 +176,6 @@ __device__ __forceinline__ void mg_wait(unsigned *cnt, unsigned target, const Mg
 }
 
 __device__ __forceinline__ float4 mg_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-// the weight stream (W1, V1, W2, V2: every byte is read by exactly ONE workgroup, once): CLO_MG_NTW = 1 marks these loads
-// nontemporal (the guide's "nt-weights" row: issued -> landed -18 % on an LDS-DMA weight stream).  A/B of round 6:
-// profiles/r06_c2_mega_nt_weights.txt.
-#ifndef CLO_MG_NTW
-#define CLO_MG_NTW 0
-#endif
-__device__ __forceinline__ float4 mg_ldw(const float *p) {
-#if CLO_MG_NTW
-  typedef float __attribute__((ext_vector_type(4))) v4;
-  const v4 v = __builtin_nontemporal_load(reinterpret_cast<const v4 *>(p));
-  return make_float4(v[0], v[1], v[2], v[3]);
-#else
-  return *reinterpret_cast<const float4 *>(p);
-#endif
-}
 __device__ __forceinline__ void mg_st4nt(float *p, const float4 &v) {
   typedef float __attribute__((ext_vector_type(4))) v4;
   __builtin_nontemporal_store(v4{v.x, v.y, v.z, v.w}, reinterpret_cast<v4 *>(p));
@@ -224,34 +186,8 @@ __device__ __forceinline__ float mg_and(float x, unsigned m) { return __uint_as_
 __device__ __forceinline__ void mg_wait_scalar(unsigned *cnt, unsigned target, const MgAbort &ab, int lane) {
   scalar_wait(cnt, target, ab.err, ab.fault, ab.limit, lane);
 }
-// arrival through the scalar path as well (s_atomic_add, no return)
-#ifndef CLO_MG_SARRIVE
-#define CLO_MG_SARRIVE 1
-#endif
+// arrival through the scalar path as well (s_atomic_add, no return; seam A only)
 __device__ __forceinline__ void mg_arrive_scalar(unsigned *cnt) { scalar_arrive(cnt); }
-// CLO_MG_SARRIVE bits as CLO_MG_SPOLL's
-#define MG_ARRIVE_B(cnt, bit)                                                   \
-  do {                                                                          \
-    if ((CLO_MG_SARRIVE) & (bit)) {                                             \
-      if (wave == 0) mg_arrive_scalar(cnt);                                     \
-    } else {                                                                    \
-      if (tid == 0) mg_arrive(cnt);                                             \
-    }                                                                           \
-  } while (0)
-#if CLO_MG_SARRIVE & 1
-#define MG_ARRIVE7(cnt) mg_arrive_scalar(cnt)
-#else
-#define MG_ARRIVE7(cnt) do { if (lane == 0) mg_arrive(cnt); } while (0)
-#endif
-// CLO_MG_SPOLL bits: 1 colA, 2 rowA, 4 rowB, 8 top, 16 colB
-#define MG_WAIT(cnt, target, bit)                                              \
-  do {                                                                          \
-    if ((CLO_MG_SPOLL) & (bit)) {                                               \
-      if (wave == 0) mg_wait_scalar((cnt), (target), c_err, lane);              \
-    } else {                                                                    \
-      if (tid == 0) mg_wait((cnt), (target), c_err);                            \
-    }                                                                           \
-  } while (0)
 
 template <bool ACCUM>
 __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
@@ -268,7 +204,6 @@ __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
 
   // ---- geometry (all splits are balanced integer splits; see mega_ok for the bounds)
   const int S1 = d1 >> 4;
-#if CLO_MG_XCD
   // Workgroup w runs on XCD w % 8 (observed, used for speed only): an XCD holds the two K ranges 2x, 2x + 1 for every
   // feature block, so a column group (the 16 workgroups that exchange a1 / delta_1) shares one L2, and the K ranges
   // are cut in PAIRS on 128-byte lines (a step = 64 B): only the cut inside a pair can fall in the middle of a
@@ -284,10 +219,6 @@ __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
     ks0 = kb * S1 / 16;
     ns = (kb + 1) * S1 / 16 - ks0;
   }
-#else
-  const int fb = w >> 4, kb = w & 15;
-  const int ks0 = kb * S1 / 16, ns = (kb + 1) * S1 / 16 - ks0;          // k16 steps of the K range
-#endif
   const int k0 = ks0 * 16, kr = ns * 16;
   const int G2 = d2 >> 3;
   const int g0 = fb * G2 / 16, ng = (fb + 1) * G2 / 16 - g0;            // feature groups of the block
@@ -304,7 +235,7 @@ __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
   const unsigned call = sy[0];
   unsigned *set = sy + 32 * (1 + (call & 1) * MG_SET_LINES);
   unsigned *c_colA = set + 32 * kb, *c_rowA = set + 32 * (16 + fb), *c_rowB = set + 32 * (32 + fb);
-  unsigned *c_colB = set + 32 * (48 + kb), *c_top = set + 32 * (64 + (CLO_MG_TOPFAN ? fb : 0));
+  unsigned *c_colB = set + 32 * (48 + kb), *c_top = set + 32 * (64 + fb);
   const MgAbort c_err{sy + 1, p.fault, p.spin_limit};
   MG_STAMP(0);
   if (w == 0) {  // zero the other set for the next call
@@ -375,7 +306,7 @@ __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
     for (int s = 0; s < MG_P1S; ++s) {
       const bool ok = s * 16 + s4 < klen;
 #pragma unroll
-      for (int g = 0; g < 2; ++g) a1v[s][g] = mg_ldw(pA1[g] + (ok ? s * 16 : 0));
+      for (int g = 0; g < 2; ++g) a1v[s][g] = mg_ld4(pA1[g] + (ok ? s * 16 : 0));
     }
   }
   // layer-2 tile: fragments [W rows ; V rows] of this wave's feature groups, step-major issue order; only
@@ -394,7 +325,7 @@ __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
 #pragma unroll
     for (int s = 0; s < MG_PRE; ++s) {
 #pragma unroll
-      for (int g = 0; g < MG_MAXG; ++g) tv[s][g] = mg_ldw(pA2[g] + min(s, ns - 1) * 16);
+      for (int g = 0; g < MG_MAXG; ++g) tv[s][g] = mg_ld4(pA2[g] + min(s, ns - 1) * 16);
     }
   }
 #pragma unroll
@@ -424,14 +355,10 @@ __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
       const float bx = mg_and(bv.x, m), by = mg_and(bv.y, m), bz = mg_and(bv.z, m), bw = mg_and(bv.w, m);
 #pragma unroll
       for (int g = 0; g < 2; ++g) {
-#if CLO_MG_ABLATE & 1
-        acc[g] += f32x4{a1v[s][g].x + bx, a1v[s][g].y + by, a1v[s][g].z + bz, a1v[s][g].w + bw};
-#else
         acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1v[s][g].x, bx, acc[g], 0, 0, 0);
         acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1v[s][g].y, by, acc[g], 0, 0, 0);
         acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1v[s][g].z, bz, acc[g], 0, 0, 0);
         acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1v[s][g].w, bw, acc[g], 0, 0, 0);
-#endif
       }
     }
 #pragma unroll
@@ -455,7 +382,7 @@ __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
     for (int s = MG_PRE; s < MG_HOLD; ++s) {
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * (MG_PACE - 1)) : "memory");
 #pragma unroll
-      for (int g = 0; g < MG_MAXG; ++g) tv[s][g] = mg_ldw(pA2[g] + min(s, ns - 1) * 16);
+      for (int g = 0; g < MG_MAXG; ++g) tv[s][g] = mg_ld4(pA2[g] + min(s, ns - 1) * 16);
     }
     MG_STAMP(3);
   } else {
@@ -500,15 +427,8 @@ __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
     }
     drain_vm();
     MG_STAMP7(18);
-#if CLO_MG_SPOLL & 1
-    MG_ARRIVE7(c_colA);
+    mg_arrive_scalar(c_colA);
     mg_wait_scalar(c_colA, 16u, c_err, lane);
-#else
-    if (lane == 0) {
-      mg_arrive(c_colA);
-      mg_wait(c_colA, 16u, c_err);
-    }
-#endif
     asm volatile("" ::: "memory");
     __builtin_amdgcn_wave_barrier();
     MG_STAMP7(19);
@@ -545,21 +465,17 @@ __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
     for (int s = 0; s < MG_MAXS; ++s) {
       if (s + MG_HOLD < MG_MAXS) {   // the steps held back during the seam are requested here, MG_HOLD steps ahead of their use
 #pragma unroll
-        for (int g = 0; g < MG_MAXG; ++g) tv[s + MG_HOLD][g] = mg_ldw(pA2[g] + min(s + MG_HOLD, ns - 1) * 16);
+        for (int g = 0; g < MG_MAXG; ++g) tv[s + MG_HOLD][g] = mg_ld4(pA2[g] + min(s + MG_HOLD, ns - 1) * 16);
       }
       if (s < ns) {
         const float4 bv = mg_ld4(pBs + s * 16);
 #pragma unroll
         for (int g = 0; g < MG_MAXG; ++g) {
           const int gl = wave * MG_MAXG + g;
-#if CLO_MG_ABLATE & 1
-          acc[g] += f32x4{tv[s][g].x + bv.x, tv[s][g].y + bv.y, tv[s][g].z + bv.z, tv[s][g].w + bv.w};
-#else
           acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(tv[s][g].x, bv.x, acc[g], 0, 0, 0);
           acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(tv[s][g].y, bv.y, acc[g], 0, 0, 0);
           acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(tv[s][g].z, bv.z, acc[g], 0, 0, 0);
           acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(tv[s][g].w, bv.w, acc[g], 0, 0, 0);
-#endif
           // branch-free copy of the W half (lanes idx < 8) into the LDS tile; other lanes hit a trash slot
           float *dst = (idx < 8 && gl < ng) ? &s_w[(gl * 8 + idx) * MG_LDW + s * 16 + s4] : &s_trash[lane * 4];
           *reinterpret_cast<float4 *>(dst) = tv[s][g];
@@ -606,8 +522,8 @@ __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
     for (int i = 0; i < MG_AUX_MAX / MG_T; ++i)
       if (i * MG_T + tid < naux) s_m[MG_M_AUX + i * MG_T + tid] = auxv[i];
     wg_barrier();
-    MG_ARRIVE_B(c_rowA, 2);
-    MG_WAIT(c_rowA, 16u, 2);
+    if (tid == 0) mg_arrive(c_rowA);
+    if (tid == 0) mg_wait(c_rowA, 16u, c_err);
     wg_barrier();
     MG_STAMP(6);
   }
@@ -670,10 +586,10 @@ __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
     drain_vm();
     wg_barrier();
     MG_STAMP(7);
-    MG_ARRIVE_B(c_rowB, 4);
+    if (tid == 0) mg_arrive(c_rowB);
     // ---- leader of the row group: sum the 16 partials, publish, arrive on the chip-wide counter
     if (kb == 0) {
-      MG_WAIT(c_rowB, 16u, 4);
+      if (tid == 0) mg_wait(c_rowB, 16u, c_err);
       wg_barrier();
       if (tid < 64) {
         f32x4 t[16];
@@ -686,13 +602,9 @@ __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
       }
       drain_vm();
       wg_barrier();
-#if CLO_MG_TOPFAN
       if (tid < 16) mg_arrive(set + 32 * (64 + tid));
-#else
-      MG_ARRIVE_B(c_top, 8);
-#endif
     }
-    MG_WAIT(c_top, 16u, 8);
+    if (wave == 0) mg_wait_scalar(c_top, 16u, c_err, lane);
     // every workgroup has read the call counter long before all leaders arrived: safe to bump it now
     if (tid == 0 && w == 0) sy[0] = call + 1;
     wg_barrier();
@@ -821,19 +733,12 @@ __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
             if (jb + u * rpp < nj) {
               const float dn[MG_NB] = {da[u].x, da[u].y, da[u].z, da[u].w, db[u].x, db[u].y, db[u].z, db[u].w};
               const f32x2 w01 = {wv[u].x, wv[u].y}, w23 = {wv[u].z, wv[u].w};
-#if CLO_MG_ABLATE & 2
-              pa[0][0] += w01 + f32x2{dn[0], dn[1]};
-              pa[0][1] += w23 + f32x2{dn[2], dn[3]};
-              pa[1][0] += f32x2{dn[4], dn[5]};
-              pa[1][1] += f32x2{dn[6], dn[7]};
-#else
 #pragma unroll
               for (int n = 0; n < MG_NB; ++n) {
                 const f32x2 dd = {dn[n], dn[n]};
                 pa[n][0] = __builtin_elementwise_fma(dd, w01, pa[n][0]);
                 pa[n][1] = __builtin_elementwise_fma(dd, w23, pa[n][1]);
               }
-#endif
             }
           }
         }
@@ -864,7 +769,7 @@ __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
       }
       drain_vm();
       wg_barrier();
-      MG_ARRIVE_B(c_colB, 16);
+      if (tid == 0) mg_arrive(c_colB);
       MG_STAMP(12);
     }
     // ---- write-only work: out_W2 tile, out_b2 / out_W3 of the finished slice, out_b3
@@ -881,17 +786,12 @@ __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
           const float4 da = mg_ld4(&s_d2[j * MG_NB]), db = mg_ld4(&s_d2[j * MG_NB + 4]);
           const float dn[MG_NB] = {da.x, da.y, da.z, da.w, db.x, db.y, db.z, db.w};
           f32x2 o01 = {0.f, 0.f}, o23 = {0.f, 0.f};
-#if CLO_MG_ABLATE & 4
-          o01 = av[0][0] + f32x2{dn[0], dn[1]} + f32x2{dn[4], dn[5]};
-          o23 = av[0][1] + f32x2{dn[2], dn[3]} + f32x2{dn[6], dn[7]};
-#else
 #pragma unroll
           for (int n = 0; n < MG_NB; ++n) {
             const f32x2 dd = {dn[n], dn[n]};
             o01 = __builtin_elementwise_fma(dd, av[n][0], o01);
             o23 = __builtin_elementwise_fma(dd, av[n][1], o23);
           }
-#endif
           float4 o = make_float4(o01.x, o01.y, o23.x, o23.y);
           float *po = p.O2 + (long)(j0 + j) * d1 + k0 + cq * 4;
           if (ACCUM) {
@@ -938,7 +838,7 @@ __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
     float4 xv[MG_NB];
 #pragma unroll
     for (int n = 0; n < MG_NB; ++n) xv[n] = mg_ld4(p.X + (long)min(n, N - 1) * d0 + (rl < lanes_r ? cq * 4 : 0));
-    MG_WAIT(c_colB, 16u, 16);
+    if (tid == 0) mg_wait(c_colB, 16u, c_err);
     // Behind the LAST wait of the launch: was any wait of this launch cut short (here or in a workgroup this one waited
     // for)?  Then what this workgroup computes is garbage, and it says so in its own output (below): a product that
     // timed out contains NaN instead of plausible numbers ("asynchronous faults", clo_common.h).  The load returns
@@ -973,15 +873,11 @@ __global__ __launch_bounds__(MG_T) void mlp_mega_kernel(const MegaArgs p) {
         const float4 da = mg_ld4(&s_m[MG_M_D1 + f * MG_NB]), db = mg_ld4(&s_m[MG_M_D1 + f * MG_NB + 4]);
         const float dn[MG_NB] = {da.x, da.y, da.z, da.w, db.x, db.y, db.z, db.w};
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-#if CLO_MG_ABLATE & 8
-        o = make_float4(xv[0].x + dn[0] + dn[4], xv[0].y + dn[1] + dn[5], xv[0].z + dn[2] + dn[6], xv[0].w + dn[3] + dn[7]);
-#else
 #pragma unroll
         for (int n = 0; n < MG_NB; ++n) {
           o.x = fmaf(dn[n], xv[n].x, o.x); o.y = fmaf(dn[n], xv[n].y, o.y);
           o.z = fmaf(dn[n], xv[n].z, o.z); o.w = fmaf(dn[n], xv[n].w, o.w);
         }
-#endif
         float *po = p.O1 + (long)(jA + f) * d0 + cq * 4;
         if (ACCUM) {
           const float4 od = mg_ld4(po);

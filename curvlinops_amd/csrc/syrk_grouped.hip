@@ -22,13 +22,7 @@ constexpr int SG_MAXP = 40;       // problems per launch (the descriptor table t
 constexpr int SG_T = 64;          // tile edge
 constexpr int SG_ROWS = 32;       // rows per LDS slice
 constexpr int SG_LD = 2 * SG_T + 4;
-#ifndef CLO_SG_MAX_CHUNKS
-#define CLO_SG_MAX_CHUNKS 64
-#endif
-#ifndef CLO_SG_PIPE
-#define CLO_SG_PIPE 0
-#endif
-constexpr int SG_MAX_CHUNKS = CLO_SG_MAX_CHUNKS;   // chunks per tile, at most (a 131072-row stem factor: 64 chunks of 2048 rows)
+constexpr int SG_MAX_CHUNKS = 64;   // chunks per tile, at most (a 131072-row stem factor: 64 chunks of 2048 rows)
 
 struct SgProb {
   const float *X;
@@ -45,10 +39,10 @@ struct SgArgs {
 };
 
 __global__ __launch_bounds__(256) void syrk_grouped_kernel(const SgArgs a) {
-  // CLO_SG_PIPE = 1: two LDS slices (one barrier per slice) and three slices in flight in registers -- measured SLOWER than
-  // the plain form (ResNet-18's 20 gradient covariances: 284 vs 188 us, gpurun_out/r6_run7): 34 KB of LDS per workgroup
-  // halve the workgroups per CU, and it is the number of resident workgroups that hides this kernel's load latency
-  __shared__ __attribute__((aligned(16))) float S2[(CLO_SG_PIPE ? 2 : 1) * SG_ROWS * SG_LD];
+  // (one LDS slice: a pipelined form with two slices and three in flight in registers measured SLOWER, ResNet-18's 20 gradient
+  // covariances 284 vs 188 us -- 34 KB of LDS per workgroup halve the workgroups per CU, and it is the number of resident
+  // workgroups that hides this kernel's load latency)
+  __shared__ __attribute__((aligned(16))) float S2[SG_ROWS * SG_LD];
   __shared__ unsigned s_last;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -122,7 +116,6 @@ __global__ __launch_bounds__(256) void syrk_grouped_kernel(const SgArgs a) {
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 
   auto k_loop = [&](auto FAST, auto DIAG) {
-#if !CLO_SG_PIPE
   float4 cur[4], nxt[4];
   if (r_begin < r_end) fetch(FAST, DIAG, r_begin, cur);
   for (long r0 = r_begin; r0 < r_end; r0 += SG_ROWS) {
@@ -137,28 +130,6 @@ __global__ __launch_bounds__(256) void syrk_grouped_kernel(const SgArgs a) {
 #pragma unroll
     for (int u = 0; u < (decltype(DIAG)::value ? 2 : 4); ++u) cur[u] = nxt[u];
   }
-#else
-  // three slices in flight in registers (the loads of slice s + 3 are issued before the MFMAs of slice s), the LDS image
-  // double-buffered: slice s + 1 is written while other waves may still read slice s - 1's neighbour -- never the same buffer
-  float4 r0v[4], r1v[4], r2v[4];
-  if (r_begin < r_end) {
-    fetch(FAST, DIAG, r_begin, r0v);
-    fetch(FAST, DIAG, r_begin + SG_ROWS, r1v);        // (rows past r_end come back as zeros)
-    fetch(FAST, DIAG, r_begin + 2 * SG_ROWS, r2v);
-  }
-  int buf = 0;
-  for (long r0 = r_begin; r0 < r_end; r0 += SG_ROWS, buf ^= 1) {
-    float *S = S2 + buf * (SG_ROWS * SG_LD);
-    stash(DIAG, r0v, S);
-#pragma unroll
-    for (int u = 0; u < (decltype(DIAG)::value ? 2 : 4); ++u) { r0v[u] = r1v[u]; r1v[u] = r2v[u]; }
-    fetch(FAST, DIAG, r0 + 3 * SG_ROWS, r2v);
-    __syncthreads();   // slice visible; everybody has finished the MFMAs of the slice before (which read the OTHER buffer)
-#pragma unroll
-    for (int s = 0; s < SG_ROWS / 2; ++s)
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(S[oa + 2 * s * SG_LD], S[ob + 2 * s * SG_LD], acc, 0, 0, 0);
-  }
-#endif
   };
   if (fast) {
     if (diag) k_loop(std::true_type{}, std::true_type{}); else k_loop(std::true_type{}, std::false_type{});
@@ -240,10 +211,8 @@ static void sg_plan(int P, const long *rows, const int *d, const int *ones, SgPl
     tile_rows += (double)pl.T[p] * (pl.T[p] + 1) / 2 * (double)rows[p];
   }
   // ~4 work items per compute unit; at least 256 rows each; at most SG_MAX_CHUNKS chunks per tile
-#ifndef CLO_SG_ITEMS_PER_CU
-#define CLO_SG_ITEMS_PER_CU 4
-#endif
-  long common = (long)(tile_rows / ((double)CLO_SG_ITEMS_PER_CU * kNumCU));
+  constexpr int items_per_cu = 4;
+  long common = (long)(tile_rows / ((double)items_per_cu * kNumCU));
   common = std::max<long>(256, cdiv(common, SG_ROWS) * SG_ROWS);
   pl.nitems = 0;
   pl.ntiles = 0;

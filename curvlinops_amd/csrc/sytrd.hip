@@ -40,9 +40,6 @@ constexpr int TD_NMAX = TD_VEC * TD_THREADS * 4 - 8;
 
 // Sum over the wave with DPP row operations; every lane returns the total.
 __device__ __forceinline__ float wave_sum_dpp(float v) {
-#ifdef CLO_TD_SHFL
-  return wave_sum(v);
-#endif
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));

@@ -1,4 +1,5 @@
-"""Phase timeline of the persistent <= 8-row kernel (library built with -DCLO_MEGA_TIMING, see tools/buildvar.sh):
+"""Phase timeline of the persistent <= 8-row kernel (library built with -DCLO_MEGA_TIMING: tools/buildmega.sh timing
+-DCLO_MEGA_TIMING):
 CLO_HIP_LIB=curvlinops_amd/lib/variants/libclo_timing.so python tools/probe_mega_timing.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
